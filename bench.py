@@ -1,7 +1,7 @@
 """bench.py -- VPT policy forward throughput on MI355X (BASELINE.json metric: frames/sec, 2x policy,
 128x128x3 frames, seq = 128).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path (MinecraftAgentPolicy.forward through libvpt_hip.so) over one batch
@@ -10,7 +10,12 @@ from the previous step (BASELINE.json configs[1]: foundation-model-2x forward on
 exchange step, so N > 1 runs N data-parallel replicas on disjoint batches (weak scaling, no collective on
 the data path); rank 0 prints ONE JSON line with the whole-job frames/s.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the headline keys (metric, value, unit, ms_per_step, dtype, ...).
+--dump-outputs DIR: after the timed steps, what the last step handed its caller (both heads' log-probs, the value prediction, the carried
+state) as DIR/<name>.npy in float32, under 64 MB in all (see dump_outputs); weights and frames are seeded, so two runs with the same
+arguments see identical inputs.  --full: every other leg below as well, on the same line.
+
+Extra objects on the line (--full only):
   roofline     : dominant kernel (vpt_conv3x3_kernel, 72 % of the forward FLOPs): algorithmic FLOPs of all
                  its launches in one step / their summed HIP-event durations, vs the 2.5 PFLOP/s dense bf16
                  MFMA peak (MI355X_MICROARCH.md).  `e2e_frac` = frames/s x 15.1016 GFLOP / peak.
@@ -31,6 +36,7 @@ under a launcher it refuses a WORLD_SIZE that differs from N, and it refuses N >
 VPT_DIST_BACKEND=gloo (tests).  The N > 1 line carries `collective_ranks` from an actual all-reduce of device tensors.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -43,6 +49,36 @@ import torch  # noqa: E402
 
 FLOP_PER_FRAME = {"1x": 3.8235e9, "2x": 15.1016e9, "3x": 33.8409e9}  # BASELINE.md §3 (t = 128; 3x at t = 256)
 MFMA_BF16_PEAK = 2.5e15
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs writes less than 64 MB in all (npy headers included)
+
+
+def dump_outputs(out_dir, pd, vpred, state):
+    """--dump-outputs: what one forward step hands its caller -- log-probs of both heads, the value prediction, and the carried state
+    (mask, K, V per block) -- as out_dir/<name>.npy in float32.  Every array gets an equal share of DUMP_BUDGET_BYTES (at most 4 MB); a
+    larger one is written as `<name>_sample.npy`, its elements at flat indices drawn from a CPU generator seeded by the name (the same
+    elements in every run and on every build).  Returns {file name: shape}."""
+    import zlib
+    import numpy as np
+    arrays = {"buttons_logprob": pd["buttons"], "camera_logprob": pd["camera"], "vpred": vpred}
+    for l, (m, (k, v)) in enumerate(state):
+        if m is not None:
+            arrays[f"state_{l}_mask"] = m
+        arrays[f"state_{l}_k"] = k
+        arrays[f"state_{l}_v"] = v
+    cap = min(1 << 20, DUMP_BUDGET_BYTES // 4 // len(arrays))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            name += "_sample"
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name + ".npy"] = list(a.shape)
+    return written
 
 
 class BoxSampler:
@@ -805,7 +841,7 @@ def _emit(obj):
     out.flush()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -813,16 +849,46 @@ def main():
     ap.add_argument("--model", default="2x")
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--seq", type=int, default=128)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--bc-steps", type=int, default=10, help="timed behavioural-cloning steps after the forward measurement (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32, < 64 MB)")
+    ap.add_argument("--full", action="store_true", help="every leg besides the headline: other format, roofline, parity, BC steps, ingest, configs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline, the other format's record and the parity legs")
+    ap.add_argument("--bc-steps", type=int, default=10, help="(--full) timed behavioural-cloning steps after the forward measurement (0: skip)")
     ap.add_argument("--bc-warmup", type=int, default=1)
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"], help="operand format of the HEADLINE value (north star: bf16 tiles); the other format is reported beside it")
-    ap.add_argument("--no-ingest", action="store_true", help="skip the host -> device ingest leg")
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp16"], help="operand format of the HEADLINE value (north star: bf16 tiles); --full reports the other beside it")
+    ap.add_argument("--no-ingest", action="store_true", help="(--full) skip the host -> device ingest leg")
     ap.add_argument("--step-overlap", type=int, default=0, help="1: PolicyEngine.overlap_steps() during the timed forward (A/B)")
     ap.add_argument("--ingest-only", action="store_true", help="(profiling) only the timed forward and the ingest leg; prints the ingest record")
-    ap.add_argument("--value-blocks", type=int, default=1, help="0: skip the repeated short forward blocks (`value_blocks` on the line)")
-    ap.add_argument("--no-dp-probe", action="store_true", help="skip bc_step.dp_path_one_rank (the data-parallel step over RCCL in a one-rank group)")
-    args = ap.parse_args()
+    ap.add_argument("--value-blocks", type=int, default=1, help="(--full) 0: skip the repeated short forward blocks (`value_blocks` on the line)")
+    ap.add_argument("--no-dp-probe", action="store_true", help="(--full) skip bc_step.dp_path_one_rank (the data-parallel step over RCCL in a one-rank group)")
+    return ap.parse_args(argv)
+
+
+def _parallelism(world, distributed, dist, collective_ranks):
+    par = f"dp{world} replicas (no collective in forward; BC step: gradient all-reduce)"
+    if distributed:
+        par += f"; torch.distributed backend={dist.get_backend()} world_size={dist.get_world_size()}" + (" (RCCL)" if dist.get_backend() == "nccl" else "")
+        par += f"; collective_ranks={collective_ranks} (sum of ones over an all-reduce of device tensors)"
+    return par
+
+
+def headline_line(args, world, B, T, elapsed, par):
+    """The contract keys: what a plain run prints, and the head of a --full line."""
+    fps = world * B * T * args.steps / elapsed
+    return {
+        "metric": "frames/sec (fwd) [+ bc_step.ms_per_step], 2x policy, 128x128x3 seq=128",
+        "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
+        "config": {"workload": f"foundation-model-{args.model} policy forward (IMPALA CNN + 4-layer banded transformer + heads), "
+                               f"batch={B} seq={T} uint8 128x128x3 frames per GPU, KV memory carried, random-init weights",
+                   "global_batch": world * B, "seq_len": T, "parallelism": par},
+        "e2e_tflops": round(fps * FLOP_PER_FRAME.get(args.model, 0) / 1e12, 1),
+        "e2e_frac_of_mfma_peak": round(fps * FLOP_PER_FRAME.get(args.model, 0) / MFMA_BF16_PEAK, 4),
+    }
+
+
+def main():
+    args = parse_args()
 
     backend = os.environ.get("VPT_DIST_BACKEND", "nccl")      # "nccl" IS RCCL on ROCm; "gloo" lets the N > 1 branch run with every rank on one GPU (tests)
     n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -894,9 +960,15 @@ def main():
     img = torch.randint(0, 256, (B, T, 128, 128, 3), generator=g, dtype=torch.uint8).to(dev)
     first = torch.zeros(B, T, dtype=torch.bool, device=dev)
 
-    def step(st):
+    last = {}
+
+    def step(st, keep=False):
+        if keep:
+            last.clear()           # the previous step's outputs are released before this step allocates, as without `keep`
         with torch.no_grad():      # inference path (a grad-enabled call would go through the autograd boundary and keep activations)
             (pd, vpred, _), st = pol({"img": img}, first, st)
+        if keep:
+            last.update(pd=pd, vpred=vpred, state=st)
         return st
 
     def barrier():
@@ -905,14 +977,14 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_forward(steps, warmup):
+    def timed_forward(steps, warmup, keep_last=False):
         state = pol.initial_state(B)
         for _ in range(warmup):
             state = step(state)
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
-            state = step(state)
+            state = step(state, keep_last)
         barrier()
         el = time.perf_counter() - t0
         if distributed:
@@ -923,9 +995,18 @@ def main():
 
     if args.step_overlap:
         pol.overlap_steps(True)
-    with BoxSampler(dev_index) as box_fwd:
-        elapsed, state = timed_forward(args.steps, args.warmup)
+    with (BoxSampler(dev_index) if args.full else contextlib.nullcontext()) as box_fwd:
+        elapsed, state = timed_forward(args.steps, args.warmup, keep_last=bool(args.dump_outputs))
     pol.overlap_steps(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["pd"], last["vpred"], last["state"])
+    last.clear()
+    if not args.full and not args.ingest_only:
+        if rank == 0:
+            _emit(headline_line(args, world, B, T, elapsed, _parallelism(world, distributed, dist, collective_ranks)))
+        if distributed:
+            dist.destroy_process_group()
+        return
     # the same measurement again in short blocks spread over the run (after the headline steps, after the instrumented step, after the BC leg): a
     # box that throttles as it warms up, or a +-2.5 % box effect, shows as the spread of these blocks on the line itself
     blocks = []
@@ -994,10 +1075,6 @@ def main():
     frames_total = world * B * T * args.steps
     fps = frames_total / elapsed
     if rank == 0:
-        par = f"dp{world} replicas (no collective in forward; BC step: gradient all-reduce)"
-        if distributed:
-            par += f"; torch.distributed backend={dist.get_backend()} world_size={dist.get_world_size()}" + (" (RCCL)" if dist.get_backend() == "nccl" else "")
-            par += f"; collective_ranks={collective_ranks} (sum of ones over an all-reduce of device tensors)"
         bms = sorted(b["ms_per_step"] for b in blocks)
         vblocks = None
         if bms:
@@ -1007,18 +1084,8 @@ def main():
                            note="short repeats of the timed forward spread over the run; `value` itself comes from the K contract steps only")
         # ---- key order: the contract keys, then the bulky detail, then -- LAST, so that the tail of stdout holds them -- parity_status, parity_mode,
         # bc_step, box, value_blocks, roofline, cpu_baseline (the driver keeps the last few KB of stdout; round 5's bf16 bc_step was cut off) ----
-        line = {
-            "metric": "frames/sec (fwd) [+ bc_step.ms_per_step], 2x policy, 128x128x3 seq=128",
-            "value": round(fps, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": head, "data": "synthetic",
-            "config": {"workload": f"foundation-model-{args.model} policy forward (IMPALA CNN + 4-layer banded transformer + heads), "
-                                   f"batch={B} seq={T} uint8 128x128x3 frames per GPU, KV memory carried, random-init weights",
-                       "global_batch": world * B, "seq_len": T, "parallelism": par},
-            "e2e_tflops": round(fps * FLOP_PER_FRAME.get(args.model, 0) / 1e12, 1),
-            "e2e_frac_of_mfma_peak": round(fps * FLOP_PER_FRAME.get(args.model, 0) / MFMA_BF16_PEAK, 4),
-            "kernels": _trim_kernels(kernels),
-        }
+        line = headline_line(args, world, B, T, elapsed, _parallelism(world, distributed, dist, collective_ranks))
+        line["kernels"] = _trim_kernels(kernels)
         tail = {"bc_step": bc, "box": box_fwd.record(), "value_blocks": vblocks, "roofline": roof}
         if world == 1 and not args.no_cpu_baseline:
             if isinstance(other_rec, dict) and "kernels" in other_rec:

@@ -1,10 +1,11 @@
 """Golden vectors of the action codec from the LIVE, UNMODIFIED reference (run in the build container only).
 
-    python tests/golden/make_golden_actions.py       # writes tests/golden/actions_seed0.npz
+    python tests/golden/make_golden_actions.py       # writes tests/golden/actions_seed0.npz and actions_fresh_seed123.npz
 
 Inputs: random factored actions, every joint index, adversarial button patterns (several buttons of one group,
 forward+back, left+right, inventory with other buttons, inventory values other than 1), camera angles incl. the clip
-range and values sitting on mu-law bin edges."""
+range and values sitting on mu-law bin edges.  actions_fresh_seed123.npz: the reference's answers on the second, independently
+drawn input set of tests/test_action_codec_cpu.py::test_oracle_matches_live_reference_on_fresh_inputs."""
 import os
 import sys
 
@@ -50,6 +51,27 @@ def main():
         out[f"disc_{tag}"] = bins
         out[f"undisc_{tag}"] = np.asarray(t.undiscretize_camera(np.arange(11)[:, None].repeat(2, 1)), dtype=np.float64)
     path = os.path.join(HERE, "actions_seed0.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, {k: v.shape for k, v in out.items()})
+    fresh(mapper)
+
+
+def fresh_inputs(seed=123):
+    rng = np.random.default_rng(seed)
+    buttons = (rng.random((2000, 20)) < 0.3).astype(np.int64)
+    camera = rng.integers(0, 11, (2000, 2)).astype(np.int64)
+    angles = rng.normal(0, 4, (5000, 2))
+    return buttons, camera, angles
+
+
+def fresh(mapper):
+    from lib.actions import ActionTransformer
+    buttons, camera, angles = fresh_inputs()
+    ff = mapper.from_factored(dict(buttons=buttons.copy(), camera=camera.copy()))
+    t = ActionTransformer(camera_binsize=2, camera_maxval=10, camera_mu=10, camera_quantization_scheme="mu_law")
+    out = dict(buttons=buttons.astype(np.int8), camera=camera.astype(np.int8), angles=angles,
+               ff_buttons=ff["buttons"][:, 0], ff_camera=ff["camera"][:, 0], disc_mu=t.discretize_camera(angles))
+    path = os.path.join(HERE, "actions_fresh_seed123.npz")
     np.savez_compressed(path, **out)
     print("wrote", path, {k: v.shape for k, v in out.items()})
 

@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_through_torchrun():
     env = dict(os.environ, VPT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", "29577", os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--bc-steps", "1", "--bc-warmup", "1", "--batch", "2", "--seq", "16", "--model", "1x"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -53,7 +53,7 @@ def test_bench_gpus_2_launches_its_own_ranks():
     never read it, so the same command line would have printed a 1-GPU number.  (gloo: both ranks share the test box's one GPU.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(VPT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--bc-steps", "1", "--bc-warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--bc-steps", "1", "--bc-warmup", "1",
            "--batch", "2", "--seq", "16", "--model", "1x"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -89,7 +89,7 @@ def test_bench_stdout_is_exactly_one_json_line_with_the_rccl_probe():
     a pipe delivers at exit -- behind the line.  bench.py points descriptor 1 at stderr and writes the line to the saved descriptor."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--bc-steps", "1", "--bc-warmup", "1", "--batch", "2", "--seq", "16",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "1", "--warmup", "1", "--bc-steps", "1", "--bc-warmup", "1", "--batch", "2", "--seq", "16",
            "--model", "1x", "--no-cpu-baseline", "--no-ingest", "--value-blocks", "0"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -98,3 +98,38 @@ def test_bench_stdout_is_exactly_one_json_line_with_the_rccl_probe():
     rec = json.loads(out)
     probe = rec["bc_step"].get("dp_path_one_rank")
     assert probe and "error" not in probe and probe["ranks"] == 1, probe          # the probe ran (so RCCL was initialised in this process)
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                 "e2e_tflops", "e2e_frac_of_mfma_peak"}
+
+
+def test_plain_run_prints_the_headline_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """Without --full the line carries the contract keys and nothing else, over exactly --steps timed steps; --dump-outputs writes the last timed
+    step's outputs in float32, and two runs with the same arguments (seeded weights and frames) write the same arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    recs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--seq", "16", "--model", "1x",
+               "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        out = p.stdout.strip()
+        assert out.startswith("{") and "\n" not in out, p.stdout[-800:]
+        recs.append(json.loads(out))
+    for rec in recs:
+        assert set(rec) == HEADLINE_KEYS, sorted(set(rec) ^ HEADLINE_KEYS)
+        assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["n_gpus"] == 1 and rec["dtype"] == "bf16" and rec["unit"] == "frames/s" and rec["higher_is_better"] is True
+        assert rec["value"] > 0 and abs(rec["value"] - 2 * 16 * 3 / (rec["ms_per_step"] * 3e-3)) / rec["value"] < 1e-2
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"buttons_logprob.npy", "camera_logprob.npy", "vpred.npy", "state_0_k.npy", "state_0_v.npy"} <= set(names), names
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) < 64e6
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=n)
+    lp = np.load(tmp_path / "a" / "buttons_logprob.npy")
+    assert lp.shape == (2, 16, 1, 8641) and np.allclose(np.exp(lp).sum(-1), 1.0, atol=1e-2)
+    assert np.load(tmp_path / "a" / "vpred.npy").shape == (2, 16, 1)

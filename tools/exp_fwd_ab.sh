@@ -3,8 +3,8 @@
 out=gpurun_out/exp_fwd_ab; mkdir -p $out
 REF=$PWD/video-pre-training_amd/build/libvpt_ref.so
 for r in 1 2; do
-  VPT_HIP_LIB=$REF timeout 600 python bench.py --steps ${VPT_AB_STEPS:-10} --warmup 3 2>/dev/null | tail -1 > $out/ref_$r.json
-  timeout 600 python bench.py --steps ${VPT_AB_STEPS:-10} --warmup 3 2>/dev/null | tail -1 > $out/new_$r.json
+  VPT_HIP_LIB=$REF timeout 600 python bench.py --full --steps ${VPT_AB_STEPS:-10} --warmup 3 2>/dev/null | tail -1 > $out/ref_$r.json
+  timeout 600 python bench.py --full --steps ${VPT_AB_STEPS:-10} --warmup 3 2>/dev/null | tail -1 > $out/new_$r.json
   python - <<P
 import json
 for t in ("ref_$r", "new_$r"):

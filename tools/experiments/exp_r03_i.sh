@@ -12,11 +12,11 @@ for lib in ref new; do
 done
 unset VPT_HIP_LIB
 for r in 1 2; do
-  VPT_HIP_LIB=$REF timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 4 2>/dev/null | tail -1 > $out/ref_$r.json
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 4 2>/dev/null | tail -1 > $out/new_$r.json
+  VPT_HIP_LIB=$REF timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 4 2>/dev/null | tail -1 > $out/ref_$r.json
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 4 2>/dev/null | tail -1 > $out/new_$r.json
 done
 for c in 512 2048; do
-  VPT_CNN_CHUNK=$c timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 0 2>/dev/null | tail -1 > $out/chunk_$c.json
+  VPT_CNN_CHUNK=$c timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --bc-steps 0 2>/dev/null | tail -1 > $out/chunk_$c.json
 done
 python - <<P
 import json, glob

@@ -3,7 +3,7 @@
 out=$PWD/gpurun_out/r03_r; mkdir -p $out
 for r in 1 2; do
   for sub in 0 64 128 256; do
-    VPT_POOL_SUBCHUNK=$sub timeout 600 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --bc-steps 0 2>/dev/null | tail -1 > $out/sub${sub}_$r.json
+    VPT_POOL_SUBCHUNK=$sub timeout 600 python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --bc-steps 0 2>/dev/null | tail -1 > $out/sub${sub}_$r.json
   done
 done
 python - <<P

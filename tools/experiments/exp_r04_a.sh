@@ -7,7 +7,7 @@ timeout 600 python -m pytest tests/test_gpu_dropin.py -q -s -k "minerl" > $out/t
 timeout 300 python tools/conv_bench.py 512 5 > $out/conv_bench.log 2>&1; grep -v "Warn\|amdgpu.ids" $out/conv_bench.log
 for r in 1 2; do
   for fp in 0 1; do
-    VPT_FUSE_POOL=$fp timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fp${fp}_$r.json 2> $out/bench_fp${fp}_$r.err
+    VPT_FUSE_POOL=$fp timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fp${fp}_$r.json 2> $out/bench_fp${fp}_$r.err
     python - <<PY
 import json
 try:

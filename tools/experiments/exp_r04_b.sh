@@ -13,7 +13,7 @@ done
 unset VPT_BENCH_SHAPES VPT_BENCH_POOL
 for r in 1 2; do
   for sub in 0 256 512; do
-    VPT_FUSE_POOL_SUB=$sub timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_sub${sub}_$r.json 2> $out/bench_sub${sub}_$r.err
+    VPT_FUSE_POOL_SUB=$sub timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_sub${sub}_$r.json 2> $out/bench_sub${sub}_$r.err
     python - <<PY
 import json
 try:

@@ -14,7 +14,7 @@ unset VPT_BENCH_POOL
 for r in 1 2; do
   for n in new resold; do
     if [ $n = new ]; then L=""; else L="VPT_HIP_LIB=$B/libvpt_$n.so"; fi
-    env $L timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err
+    env $L timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_${n}_$r.json 2> $out/bench_${n}_$r.err
     python - <<PY
 import json
 try:

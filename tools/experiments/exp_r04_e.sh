@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py -q -x -s -k "folded or po
 timeout 900 python -m pytest tests/test_gpu_policy.py tests/test_gpu_configs.py -q -x -s -k "chunks_vs_golden or full_chunk or config2_sequence or idm_4x_forward" > $out/t2.log 2>&1; echo "t2 rc=$?"; grep -E "passed|failed|Error|PARITY|assert" $out/t2.log | cut -c1-260 | tail -24
 for r in 1 2; do
   for fn in 0 1; do
-    VPT_FOLD_N=$fn timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fn${fn}_$r.json 2> $out/bench_fn${fn}_$r.err
+    VPT_FOLD_N=$fn timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fn${fn}_$r.json 2> $out/bench_fn${fn}_$r.err
     python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py -q -x -s -k "folded or po
 timeout 900 python -m pytest tests/test_gpu_policy.py tests/test_gpu_configs.py -q -x -s -k "chunks_vs_golden or full_chunk or config2_sequence or idm_4x_forward or wide_models" > $out/t2.log 2>&1; echo "t2 rc=$?"; grep -E "passed|failed|Error|assert" $out/t2.log | cut -c1-260 | tail -8
 for r in 1 2; do
   for fs in 0 1; do
-    VPT_FOLD_STATS=$fs timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fs${fs}_$r.json 2> $out/bench_fs${fs}_$r.err
+    VPT_FOLD_STATS=$fs timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_fs${fs}_$r.json 2> $out/bench_fs${fs}_$r.err
     python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ for cfg in "VPT_FOLD_N=0 VPT_FUSE_POOL=0 VPT_FOLD_DENSE=0" "VPT_FOLD_N=0 VPT_FUS
 done
 timeout 900 python -m pytest tests/test_gpu_policy.py tests/test_gpu_configs.py -q -x -k "chunks_vs_golden or full_chunk or idm_4x_forward or wide_models" > $out/t2.log 2>&1; echo "t2 rc=$?"; grep -E "passed|failed|Error|assert" $out/t2.log | cut -c1-300 | tail -5
 for r in 1 2; do for fd in 0 1; do
-    VPT_FOLD_DENSE=$fd timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_$fd_$r.json 2> $out/bench_$r.err
+    VPT_FOLD_DENSE=$fd timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_$fd_$r.json 2> $out/bench_$r.err
     python - <<PY
 import json
 d=json.loads(open("$out/bench_$fd_$r.json").read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ for r in 1 2 3; do
     VPT_BENCH_TILING=$t VPT_BENCH_POOL=0 timeout 300 python tools/conv_bench.py 2>&1 | grep -v "^$" | tee $out/cb_${t}_$r.log
   done
 done
-timeout 600 python bench.py --steps 6 --warmup 2 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --steps 6 --warmup 2 > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r04_l/bench.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."; out=gpurun_out/r04_o; mkdir -p $out
 for r in 1 2; do
   for v in 1 0; do
-    VPT_LINEAR_256=$v timeout 600 python bench.py --steps 6 --warmup 2 --bc-steps 3 --bc-warmup 1 --no-cpu-baseline > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err
+    VPT_LINEAR_256=$v timeout 600 python bench.py --full --steps 6 --warmup 2 --bc-steps 3 --bc-warmup 1 --no-cpu-baseline > $out/bench_${v}_$r.json 2> $out/bench_${v}_$r.err
     python - <<PY
 import json
 d=json.loads(open("$out/bench_${v}_$r.json").read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ timeout 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_policy.py 
 for r in 1 2; do
   for v in "" ref; do
     lib=""; [ -n "$v" ] && lib="$PWD/video-pre-training_amd/build/libvpt_$v.so"
-    VPT_HIP_LIB=$lib timeout 600 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_${v:-new}_$r.json 2> $out/bench_${v:-new}_$r.err
+    VPT_HIP_LIB=$lib timeout 600 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/bench_${v:-new}_$r.json 2> $out/bench_${v:-new}_$r.err
     python - <<PY
 import json
 d=json.loads(open("$out/bench_${v:-new}_$r.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."; out=gpurun_out/r04_x; mkdir -p $out
 run() { # label env...
   local label=$1; shift
-  env "$@" timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/b.json 2> $out/b.err
+  env "$@" timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/b.json 2> $out/b.err
   python - <<PY
 import json
 d=json.loads(open("$out/b.json").read().strip().splitlines()[-1])

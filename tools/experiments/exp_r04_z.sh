@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."; out=gpurun_out/r04_z; mkdir -p $out
 for r in 1 2; do
   for sk in 16 32 8; do
-    VPT_DENSE_SPLITK=$sk timeout 300 python bench.py --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/b.json 2> $out/b.err
+    VPT_DENSE_SPLITK=$sk timeout 300 python bench.py --full --steps 6 --warmup 2 --bc-steps 0 --no-cpu-baseline > $out/b.json 2> $out/b.err
     python - <<PY
 import json
 d=json.loads(open("$out/b.json").read().strip().splitlines()[-1])

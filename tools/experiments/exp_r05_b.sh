@@ -11,8 +11,8 @@ for r in 1 2; do
 done
 R04=$PWD/video-pre-training_amd/build/libvpt_r04.so
 for r in 1 2; do
-  echo "== r04 forward round $r"; VPT_HIP_LIB=$R04 timeout 300 python bench.py --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'], {k: v['ms'] for k, v in d['kernels'].items() if v['ms'] > 0.25})"
-  echo "== new forward round $r"; timeout 300 python bench.py --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'], {k: v['ms'] for k, v in d['kernels'].items() if v['ms'] > 0.25})"
+  echo "== r04 forward round $r"; VPT_HIP_LIB=$R04 timeout 300 python bench.py --full --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'], {k: v['ms'] for k, v in d['kernels'].items() if v['ms'] > 0.25})"
+  echo "== new forward round $r"; timeout 300 python bench.py --full --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'], {k: v['ms'] for k, v in d['kernels'].items() if v['ms'] > 0.25})"
 done
 timeout 300 python tools/ingest_probe.py 2>&1 | grep -v amdgpu.ids | tail -8
 GPU_MAX_HW_QUEUES=8 timeout 300 python tools/ingest_probe.py 2>&1 | grep -v amdgpu.ids | tail -4

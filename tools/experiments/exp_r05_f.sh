@@ -9,7 +9,7 @@ for r in 1 2; do
   VPT_HIP_LIB=$REF timeout 300 python tools/bc_bench.py --steps 3 --streams1 2>&1 | grep -v amdgpu.ids > $out/ref_$r.log; echo "== ref_$r"; grep -E "^BC step|linear_wgrad|linear_forward" $out/ref_$r.log
   timeout 300 python tools/bc_bench.py --steps 3 --streams1 2>&1 | grep -v amdgpu.ids > $out/new_$r.log; echo "== new_$r"; grep -E "^BC step|linear_wgrad|linear_forward" $out/new_$r.log
 done
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; python - <<P
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; python - <<P
 import json
 d = json.loads(open("$out/bench.json").read().strip().splitlines()[-1])
 print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["bc_step"]["ms_per_step"], d["bc_step"]["kernels_ms"])

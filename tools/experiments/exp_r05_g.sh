@@ -10,6 +10,6 @@ for r in 1 2; do
   echo "== new conv_bench $r"; timeout 300 python tools/conv_bench.py 512 2>&1 | grep -E "median|fused"
 done
 for r in 1 2 3; do
-  echo "== ref forward $r"; VPT_HIP_LIB=$REF timeout 300 python bench.py --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'])"
-  echo "== new forward $r"; timeout 300 python bench.py --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'])"
+  echo "== ref forward $r"; VPT_HIP_LIB=$REF timeout 300 python bench.py --full --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'])"
+  echo "== new forward $r"; timeout 300 python bench.py --full --steps 8 --warmup 2 --bc-steps 0 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['by_mode'])"
 done

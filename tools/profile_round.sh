@@ -7,10 +7,10 @@ export TMPDIR=/tmp
 cd /tmp
 B="python $GRAFT_REPO_ROOT/bench.py"
 # (1) forward only, single CNN stream, per format: per-launch durations of vpt_conv3x3_kernel comparable with bench.py's HIP events
-VPT_CNN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwd1 -- $B --steps 3 --warmup 1 --bc-steps 0 --no-cpu-baseline > $out/fwd1_bench.json 2> $out/fwd1.err
-VPT_CNN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwd1_fp16 -- $B --precision fp16 --steps 3 --warmup 1 --bc-steps 0 --no-cpu-baseline > $out/fwd1_fp16_bench.json 2> $out/fwd1_fp16.err
+VPT_CNN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwd1 -- $B --full --steps 3 --warmup 1 --bc-steps 0 --no-cpu-baseline > $out/fwd1_bench.json 2> $out/fwd1.err
+VPT_CNN_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwd1_fp16 -- $B --full --precision fp16 --steps 3 --warmup 1 --bc-steps 0 --no-cpu-baseline > $out/fwd1_fp16_bench.json 2> $out/fwd1_fp16.err
 # (2) default forward (3 streams) + BC steps
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwdbc -- $B --steps 2 --warmup 1 --bc-steps 2 --bc-warmup 1 --no-cpu-baseline > $out/fwdbc_bench.json 2> $out/fwdbc.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/fwdbc -- $B --full --steps 2 --warmup 1 --bc-steps 2 --bc-warmup 1 --no-cpu-baseline > $out/fwdbc_bench.json 2> $out/fwdbc.err
 if [ -z "$VPT_PROF_SKIP_PMC" ]; then
 # (3) PMC passes on the conv micro-benchmark, both formats (separate passes: SQ counters, GRBM)
 for p in bf16 fp16; do
@@ -23,11 +23,11 @@ VPT_BENCH_TILING=throughput32 VPT_BENCH_POOL=0 VPT_PRECISION=bf16 rocprofv3 --ke
 VPT_BENCH_TILING=throughput32 VPT_BENCH_POOL=0 VPT_PRECISION=bf16 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE GRBM_COUNT --output-format csv -d $out/pmc_grbm_bf16_t32 -- python $GRAFT_REPO_ROOT/tools/conv_bench.py 256 2 > $out/pmc_grbm_bf16_t32.log 2>&1
 fi
 # (4) HBM traffic of the conv kernel over one bench step (FETCH_SIZE x2 on gfx950, MI355X_MICROARCH.md)
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- $B --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_fetch.json 2> $out/pmc_fetch.err
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- $B --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_write.json 2> $out/pmc_write.err
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- $B --full --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_fetch.json 2> $out/pmc_fetch.err
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- $B --full --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_write.json 2> $out/pmc_write.err
 # ... and in the parity mode (fp16 operands: same bytes by construction; measured, not assumed)
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_fp16 -- $B --precision fp16 --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_fetch_fp16.json 2> $out/pmc_fetch_fp16.err
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_fp16 -- $B --precision fp16 --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_write_fp16.json 2> $out/pmc_write_fp16.err
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_fp16 -- $B --full --precision fp16 --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_fetch_fp16.json 2> $out/pmc_fetch_fp16.err
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_fp16 -- $B --full --precision fp16 --steps 1 --warmup 0 --bc-steps 0 --no-cpu-baseline > $out/pmc_write_fp16.json 2> $out/pmc_write_fp16.err
 fi
 # (5) the BC step on ONE stream (per-kernel durations without cross-stream overlap: the table DESIGN.md section 5 quotes), round 5
 VPT_BC_STREAMS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bc1 -- python $GRAFT_REPO_ROOT/tools/bc_bench.py --steps 2 --streams1 > $out/bc1.log 2> $out/bc1.err
