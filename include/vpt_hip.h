@@ -241,6 +241,20 @@ int vpt_masked_attention_forward(const float* qkvr, const float* kmem, const flo
                                  const float* b_nd, void* out, int B, int t, int heads, int hid, int ld,
                                  int maxlen, int causal, void* stream);
 
+/* vpt_masked_attention_forward (causal = 1) with episode starts honoured at EVERY frame of the chunk, not only at t = 0: what
+ * MaskedAttention.forward (lib/masked_attention.py:161-178) computes when the same frames are stepped one at a time with one hidden state per
+ * episode, as the BC loop does (behavioural_cloning.py:95-112).  qlo int32 [B*t] (vpt_episode_bounds): query i sees row j of [memory ; chunk]
+ * iff it lies in the band, j >= qlo[i], and (j >= maxlen or memvalid[j]); memvalid is then the plain state_mask (qlo covers first[:,0]). */
+int vpt_masked_attention_forward_episodes(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
+                                          const float* b_nd, void* out, const int32_t* qlo, int B, int t, int heads, int hid, int ld,
+                                          int maxlen, void* stream);
+
+/* Episode bounds of a chunk for the two *_episodes entry points (lib/masked_attention.py:161-178 applied per frame, behavioural_cloning.py:95-112):
+ * first / state_mask: bool bytes [B][t] / [B][maxlen].  qlo int32 [B][t] = maxlen + (latest p <= i with first[b][p]), or 0 when there is none;
+ * mask_out bool bytes [B][maxlen] = the next state mask: kept row j = t + r is valid iff j >= qlo[b][t-1] and (j >= maxlen or state_mask[b][j])
+ * (the per-frame form of lib/masked_attention.py:86-92).  Either output may be NULL; mask_out must not alias state_mask.  t >= 1. */
+int vpt_episode_bounds(const uint8_t* first, const uint8_t* state_mask, int32_t* qlo, uint8_t* mask_out, int B, int t, int maxlen, void* stream);
+
 /* SelfAttentionLayer.update_state (lib/xf.py:366-391): kout/vout = last maxlen rows of [memory ; new]. */
 int vpt_kv_memory_update(const float* qkvr, const float* kmem, const float* vmem, float* kout, float* vout,
                          int B, int t, int hid, int ld, int maxlen, void* stream);
@@ -356,6 +370,12 @@ int vpt_column_sum(const void* x_bf16, float* out, float* partials, int M, int N
 int vpt_masked_attention_backward(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
                                   const float* b_nd, const float* dout, float* dqkvr, float* db_nd, float* dkv_slab, float* dbnd_slab,
                                   int B, int t, int heads, int hid, int ld, int maxlen, void* stream);
+
+/* Backward of vpt_masked_attention_forward_episodes: the same kernel with the forward's qlo (lib/masked_attention.py:161-178 per frame,
+ * behavioural_cloning.py:95-112); keys outside a query's episode have P = 0 exactly and receive no gradient from it. */
+int vpt_masked_attention_backward_episodes(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
+                                           const float* b_nd, const float* dout, float* dqkvr, float* db_nd, float* dkv_slab, float* dbnd_slab,
+                                           const int32_t* qlo, int B, int t, int heads, int hid, int ld, int maxlen, void* stream);
 
 /* ---- backward of the IMPALA CNN (behavioural_cloning.py:117-119 obtains these from torch autograd) ---- */
 

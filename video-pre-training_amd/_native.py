@@ -78,6 +78,9 @@ SIGNATURES = {
     "vpt_act_epilogue": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P],
     "vpt_clip_frames": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P],
     "vpt_debug_poison_lds": [_P],
+    "vpt_episode_bounds": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "vpt_masked_attention_forward_episodes": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vpt_masked_attention_backward_episodes": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
 }
 
 

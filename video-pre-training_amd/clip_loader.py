@@ -155,6 +155,12 @@ class DataLoader:
                     yield trajectory_id, out[k], steps.actions[lo + k]
             pos += len(chunk)
 
+    def next_lane_item(self, lane: int):
+        """The next (trajectory_id, frame, action) of ONE lane, or None once that lane has nothing left and no recording remains
+        unassigned.  For callers that keep a lane's stream together instead of interleaving the lanes (sequence_batcher.SequenceBatcher);
+        `batch_size` and `n_steps_processed` belong to the round-robin iteration below and are not touched."""
+        return self._lanes[lane].next_item()
+
     # ---- iteration (data_loader.py:195-217) -----------------------------------------------------------------------------
     def __iter__(self):
         return self

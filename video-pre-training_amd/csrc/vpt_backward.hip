@@ -294,7 +294,8 @@ extern "C" int vpt_colsum_launch(const VptColsumArgs* a, hipStream_t stream) {
 #define AB_BP 133                                         // pitch of a b_nd row in LDS: odd, so that ten lanes reading one offset of ten DIFFERENT rows (the
                                                           // dR loop) hit ten banks -- at pitch maxlen = 128 they all hit one (47 % of this kernel's LDS cycles
                                                           // were bank conflicts in the round-3 PMC survey)
-#define AB_PT_OFF ((AB_B_OFF + 10 * AB_BP + 3) & ~3)      // partial tiles of key tile 4: [wave][16][64]
+#define AB_QL_OFF (AB_B_OFF + 10 * AB_BP)                 // the tile's 32 qlo values (ints)
+#define AB_PT_OFF ((AB_QL_OFF + ATT_QT + 3) & ~3)         // partial tiles of key tile 4: [wave][16][64]
 #define AB_FLOATS (AB_PT_OFF + 4 * 16 * 64)
 
 // Round 2: every contraction runs on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) with its operands taken straight from global
@@ -312,6 +313,7 @@ __global__ __launch_bounds__(256, 2) void vpt_attn_bwd_kernel(VptAttnBwdArgs a) 
   float* Rs = sm + AB_R_OFF;
   float* Bs = sm + AB_B_OFF;
   float* Pt = sm + AB_PT_OFF;
+  int* Ql = (int*)(sm + AB_QL_OFF);
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, hi = lane >> 5;
@@ -328,6 +330,7 @@ __global__ __launch_bounds__(256, 2) void vpt_attn_bwd_kernel(VptAttnBwdArgs a) 
     Rs[idx] = (q0 + r < t) ? a.qkvr[(tok0 + q0 + r) * a.ld + 3 * hid + h * 10 + n] : 0.f;
   }
   for (int idx = tid; idx < 10 * maxlen; idx += 256) { const int n = idx / maxlen; Bs[n * AB_BP + (idx - n * maxlen)] = a.b_nd[idx]; }
+  if (tid < ATT_QT) Ql[tid] = (a.qlo && q0 + tid < t) ? a.qlo[tok0 + q0 + tid] : 0;      // as the forward kernel: rows below Ql[qi] are invisible
   __syncthreads();
 
   // row j of [memory ; chunk] -> its K (which = 1) / V (which = 2) row of this head, or null beyond the chunk
@@ -396,6 +399,7 @@ __global__ __launch_bounds__(256, 2) void vpt_attn_bwd_kernel(VptAttnBwdArgs a) 
     const int j = jbase + kk;
     bool vis = (q0 + qi) < t && off >= 0 && off < maxlen;
     if (vis && j < maxlen) vis = memv[j] != 0;
+    vis = vis && j >= Ql[qi];
     float sc = -3.0e38f;
     if (vis) {
       float rb = 0.f;

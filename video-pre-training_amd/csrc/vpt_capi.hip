@@ -420,6 +420,23 @@ int vpt_masked_attention_forward(const float* qkvr, const float* kmem, const flo
   CHECK_LAUNCH(vpt_attn_launch(&a, (hipStream_t)stream), "vpt_masked_attention_forward");
 }
 
+int vpt_masked_attention_forward_episodes(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
+                                          const float* b_nd, void* out, const int32_t* qlo, int B, int t, int heads, int hid, int ld,
+                                          int maxlen, void* stream) {
+  if (!qlo) return fail(-1, "vpt_masked_attention_forward_episodes: qlo ([B*t] int32, vpt_episode_bounds) is required");
+  VptAttnArgs a = {};
+  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = memvalid; a.b_nd = b_nd; a.out = (vpt_op16*)out; a.qlo = qlo;
+  a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = 1;
+  CHECK_LAUNCH(vpt_attn_launch(&a, (hipStream_t)stream), "vpt_masked_attention_forward_episodes");
+}
+
+int vpt_episode_bounds(const uint8_t* first, const uint8_t* state_mask, int32_t* qlo, uint8_t* mask_out, int B, int t, int maxlen, void* stream) {
+  if (!first || B <= 0 || t < 1 || maxlen < 1) return fail(-1, "vpt_episode_bounds: first [B][t] with B, t, maxlen >= 1 is required");
+  if (mask_out && !state_mask) return fail(-1, "vpt_episode_bounds: mask_out needs state_mask");
+  if (mask_out && mask_out == state_mask) return fail(-1, "vpt_episode_bounds: mask_out must not alias state_mask");
+  CHECK_LAUNCH(vpt_episode_bounds_launch(first, state_mask, qlo, mask_out, B, t, maxlen, (hipStream_t)stream), "vpt_episode_bounds");
+}
+
 int vpt_masked_attention_step(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* state_mask, const uint8_t* first,
                               const float* b_nd, void* out, float* kout, float* vout, uint8_t* mask_out,
                               int B, int heads, int hid, int ld, int maxlen, void* stream) {
@@ -554,6 +571,18 @@ int vpt_masked_attention_backward(const float* qkvr, const float* kmem, const fl
   a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = memvalid; a.b_nd = b_nd; a.dout = dout;
   a.dqkvr = dqkvr; a.db_nd = db_nd; a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen;
   CHECK_LAUNCH(vpt_attn_bwd_launch(&a, (hipStream_t)stream), "vpt_masked_attention_backward");
+}
+
+int vpt_masked_attention_backward_episodes(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
+                                           const float* b_nd, const float* dout, float* dqkvr, float* db_nd, float* dkv_slab, float* dbnd_slab,
+                                           const int32_t* qlo, int B, int t, int heads, int hid, int ld, int maxlen, void* stream) {
+  if (!dkv_slab || !dbnd_slab) return fail(-1, "vpt_masked_attention_backward_episodes: the dkv_slab / dbnd_slab workspaces are required");
+  if (!qlo) return fail(-1, "vpt_masked_attention_backward_episodes: qlo ([B*t] int32, vpt_episode_bounds) is required");
+  VptAttnBwdArgs a = {};
+  a.dkv_slab = dkv_slab; a.dbnd_slab = dbnd_slab; a.qlo = qlo;
+  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = memvalid; a.b_nd = b_nd; a.dout = dout;
+  a.dqkvr = dqkvr; a.db_nd = db_nd; a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen;
+  CHECK_LAUNCH(vpt_attn_bwd_launch(&a, (hipStream_t)stream), "vpt_masked_attention_backward_episodes");
 }
 
 }  // extern "C"

@@ -177,6 +177,8 @@ struct VptAttnArgs {
   const float* b_nd;       // [10][maxlen]
   vpt_op16* out;           // [B*t][hid]
   int B, t, heads, hid, ld, maxlen, causal;
+  const int32_t* qlo;      // optional [B*t] (causal only): the lowest row of [memory ; chunk] a query may see -- episode starts honoured at every
+                           // frame (vpt_episode_bounds_kernel); null = only what memvalid says
 };
 
 struct VptKvUpdateArgs {
@@ -359,6 +361,7 @@ struct VptAttnBwdArgs {
   float* dkv_slab;         // [5][B*t][2 hid] workspace: per query tile pieces of dK / dV (vpt_attn_bwd_dkv_floats)
   float* dbnd_slab;        // workspace: one db_nd row per workgroup + the slab sum's scratch (vpt_attn_bwd_dbnd_floats)
   int B, t, heads, hid, ld, maxlen;
+  const int32_t* qlo;      // optional [B*t], as VptAttnArgs::qlo (the forward's)
 };
 
 struct VptAdamTensor {      // one parameter tensor of a multi-tensor Adam step (device array, sorted by first_block)
@@ -417,6 +420,7 @@ int vpt_act_epilogue_launch(const int64_t* act_b, const int64_t* act_c, const fl
                             float scale, float shift, int64_t* keep, uint8_t* nan_flag, uint64_t* rng_state, int B, hipStream_t s);
 int vpt_uniform_noise_launch(const uint64_t* rng_state, uint32_t rng_stream, float* out, int M, int n, hipStream_t s);
 int vpt_attn_bwd_launch(const VptAttnBwdArgs* a, hipStream_t s);
+int vpt_episode_bounds_launch(const uint8_t* first, const uint8_t* state_mask, int32_t* qlo, uint8_t* mask_out, int B, int t, int maxlen, hipStream_t s);
 long vpt_attn_bwd_dkv_floats(int B, int t, int hid);
 long vpt_attn_bwd_dbnd_floats(int B, int t, int heads, int maxlen);
 long vpt_colsum_partial_floats(int M, int N);

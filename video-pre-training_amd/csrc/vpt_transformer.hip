@@ -72,7 +72,8 @@ extern "C" int vpt_layernorm_launch(const VptLayerNormArgs* a, hipStream_t strea
 #define ATT_R_OFF (ATT_S_OFF + ATT_QT * ATT_SS)
 #define ATT_B_OFF (ATT_R_OFF + ATT_QT * 10)
 #define ATT_SC_OFF (ATT_B_OFF + 10 * 129)
-#define ATT_PT_OFF ((ATT_SC_OFF + ATT_QT + 3) & ~3)       // partial logits of key tile 4: [wave][16][64]
+#define ATT_QL_OFF (ATT_SC_OFF + ATT_QT)                   // the tile's 32 qlo values (ints)
+#define ATT_PT_OFF ((ATT_QL_OFF + ATT_QT + 3) & ~3)       // partial logits of key tile 4: [wave][16][64]
 #define ATT_FLOATS (ATT_PT_OFF + 4 * 16 * 64)
 
 __global__ __launch_bounds__(256) void vpt_attn_kernel(VptAttnArgs a) {
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(256) void vpt_attn_kernel(VptAttnArgs a) {
   float* Rs = sm + ATT_R_OFF;
   float* Bs = sm + ATT_B_OFF;
   float* Sc = sm + ATT_SC_OFF;
+  int* Ql = (int*)(sm + ATT_QL_OFF);
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b = blockIdx.y / a.heads, h = blockIdx.y - b * a.heads;
@@ -97,6 +99,8 @@ __global__ __launch_bounds__(256) void vpt_attn_kernel(VptAttnArgs a) {
     Rs[idx] = (a.causal && q0 + r < t) ? a.qkvr[(tok0 + q0 + r) * a.ld + 3 * hid + h * 10 + n] : 0.f;
   }
   for (int idx = tid; idx < 10 * maxlen; idx += 256) Bs[idx] = a.b_nd[idx];
+  // per-frame episode starts: query qi sees rows >= Ql[qi] only (0 = no bound: every band row is >= 1)
+  if (tid < ATT_QT) Ql[tid] = (a.qlo && q0 + tid < t) ? a.qlo[tok0 + q0 + tid] : 0;
   __syncthreads();
 
   // ---- logits on the fp32 matrix cores (v_mfma_f32_32x32x2_f32): D[query][key] = sum_d Q[query][d] K[key][d] ----
@@ -151,6 +155,7 @@ __global__ __launch_bounds__(256) void vpt_attn_kernel(VptAttnArgs a) {
       const int j = jbase + kk;
       bool vis = a.causal ? (qvalid && off >= 0 && off < maxlen) : (qvalid && kk < t);
       if (vis && a.causal && j < maxlen) vis = a.memvalid[(size_t)b * maxlen + j] != 0;
+      vis = vis && j >= Ql[qi];
       float sc = -3.0e38f;
       if (vis) {
         float rb = 0.f;
@@ -222,6 +227,7 @@ __global__ __launch_bounds__(256) void vpt_attn_kernel(VptAttnArgs a) {
 extern "C" int vpt_attn_launch(const VptAttnArgs* a, hipStream_t stream) {
   if (a->hid != a->heads * ATT_DH) return -1;
   if (a->causal ? (a->maxlen < 1 || a->maxlen > 129) : (a->maxlen != 0 || a->t > ATT_NK)) return -1;
+  if (a->qlo && !a->causal) return -1;     // episode bounds are rows of [memory ; chunk]: the banded path only
   static unsigned long long optin_done = 0;
   const size_t lds = ATT_FLOATS * sizeof(float);
   if (!vpt_lds_optin((const void*)vpt_attn_kernel, (int)lds, &optin_done)) return -4;
@@ -357,6 +363,45 @@ extern "C" int vpt_attn_step_launch(const VptAttnArgs* a, const uint8_t* state_m
   VptAttnStepExtra x;
   x.state_mask = state_mask; x.first = first; x.mask_out = mask_out; x.kout = kout; x.vout = vout; x.done = done;
   hipLaunchKernelGGL(vpt_attn_step_kernel, dim3((unsigned)(a->B * a->heads)), dim3(256), 0, stream, *a, x);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Episode starts at ANY frame of a chunk (the reference's BC loop steps one frame at a time with one hidden state per episode,
+// behavioural_cloning.py:95-112, so lib/masked_attention.py:161-178 sees every `first`): in row coordinates of [memory ; chunk]
+//   qlo[b][i]      = maxlen + (latest p <= i with first[b][p]), 0 when there is none -- the lowest row query i may see;
+//   mask_out[b][r] = kept row j = t + r is valid: j >= qlo[b][t-1] and (j >= maxlen or state_mask[b][j]).
+// One wavefront per sequence; the scan runs over 64-frame slices: a ballot of the flags, the highest set bit at or below the lane,
+// and the last start of the earlier slices carried along.  Either output may be null.
+__global__ __launch_bounds__(64) void vpt_episode_bounds_kernel(const uint8_t* first, const uint8_t* state_mask, int32_t* qlo, uint8_t* mask_out,
+                                                                int t, int maxlen) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const uint8_t* f = first + (size_t)b * t;
+  int carry = -1;                                     // latest episode start among the frames of the slices done so far
+  for (int p0 = 0; p0 < t; p0 += 64) {                // (wave-uniform trip count: the ballot sees all 64 lanes)
+    const int p = p0 + lane;
+    const bool fl = p < t && f[p] != 0;
+    const unsigned long long flags = __ballot(fl);
+    const unsigned long long below = flags & (~0ull >> (63 - lane));       // bits 0 .. lane
+    const int s = below ? p0 + 63 - __clzll((long long)below) : carry;
+    if (qlo && p < t) qlo[(size_t)b * t + p] = s >= 0 ? maxlen + s : 0;
+    if (flags) carry = p0 + 63 - __clzll((long long)flags);
+  }
+  if (mask_out) {
+    const int lo = carry >= 0 ? maxlen + carry : 0;   // = qlo[b][t-1]
+    for (int r = lane; r < maxlen; r += 64) {
+      const long j = (long)t + r;
+      mask_out[(size_t)b * maxlen + r] = (j >= lo && (j >= maxlen || state_mask[(size_t)b * maxlen + j] != 0)) ? 1 : 0;
+    }
+  }
+}
+
+extern "C" int vpt_episode_bounds_launch(const uint8_t* first, const uint8_t* state_mask, int32_t* qlo, uint8_t* mask_out, int B, int t, int maxlen,
+                                         hipStream_t stream) {
+  if (!first || B <= 0 || t < 1 || maxlen < 1 || (long)t + maxlen > 0x7fffffffL) return -1;
+  if (mask_out && (!state_mask || mask_out == state_mask)) return -1;      // a lane reads row t + r while another writes row r
+  if (!qlo && !mask_out) return 0;
+  hipLaunchKernelGGL(vpt_episode_bounds_kernel, dim3((unsigned)B), dim3(64), 0, stream, first, state_mask, qlo, mask_out, t, maxlen);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

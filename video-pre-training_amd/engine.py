@@ -72,6 +72,17 @@ class _NullCtx:
 PRECISIONS = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
+EPISODE_STARTS = ("chunk", "frame")
+
+
+def check_episode_starts(episode_starts: str) -> str:
+    """"chunk": `first` is honoured at t = 0 of a call only (one lib/masked_attention.py:161-178 call, the default); "frame": at every
+    frame, i.e. what stepping the same frames one at a time computes (behavioural_cloning.py:95-112)."""
+    if episode_starts not in EPISODE_STARTS:
+        raise ValueError(f"episode_starts must be one of {EPISODE_STARTS}, got {episode_starts!r}")
+    return episode_starts
+
+
 def resolve_precision(precision: Optional[str]) -> str:
     """precision=None -> env VPT_PRECISION -> "fp16", the parity mode (log-probs within the north star's 1e-3 of the fp32
     reference, exact actions outside a 10x narrower noise band).  "bf16" -- the north star's "MFMA bf16 tiles", what bench.py
@@ -511,8 +522,10 @@ class PolicyEngine:
 
     @torch.no_grad()
     def forward(self, img_u8: torch.Tensor, first: torch.Tensor, state_in: List, mask: Optional[dict] = None,
-                sample: Optional[str] = None, inplace_state: bool = False, act_tail: Optional[tuple] = None):
-        """mask: optional {"buttons" / "camera": bool [B,T,1,n]} availability masks (obs["mask"], lib/policy.py:257-266).
+                sample: Optional[str] = None, inplace_state: bool = False, act_tail: Optional[tuple] = None, episode_starts: str = "chunk"):
+        """episode_starts: "chunk" (default) honours first[:, 0] only; "frame" honours first[b, t] at every t -- no frame attends across an
+        episode start inside the chunk, and the state mask that leaves the call knows where the last one was (ops.episode_bounds).
+        mask: optional {"buttons" / "camera": bool [B,T,1,n]} availability masks (obs["mask"], lib/policy.py:257-266).
         sample: None, "deterministic" or "stochastic" -- CategoricalActionHead.sample + logprob fused into the head kernel
         (lib/action_head.py:176-207); adds out["action"] (int64 [B,T,1] per head) and out["action_log_prob"] ([B,T]).
         inplace_state (T = 1 only): state_out IS state_in, masks included, updated in place (the captured acting graph's static state).
@@ -521,6 +534,7 @@ class PolicyEngine:
         views of the record."""
         if not self.packed:
             raise RuntimeError("PolicyEngine.pack(state_dict) must be called before forward")
+        check_episode_starts(episode_starts)
         cfg, w = self.cfg, self.w
         bsz, t = img_u8.shape[:2]
         hid, heads, maxlen = cfg["hidsize"], cfg["heads"], cfg["maxlen"]
@@ -540,8 +554,12 @@ class PolicyEngine:
         step = t == 1 and maxlen <= ops.ATTENTION_STEP_MAXLEN     # acting step: attention, memory shift and mask update in one launch
         if inplace_state and not step:
             raise ValueError("inplace_state is the acting step's option (T = 1)")
+        per_frame = episode_starts == "frame" and not step       # (the step kernel honours its one frame's `first` already)
         if step:
             first8 = first[:, 0].contiguous().view(torch.uint8)
+        elif per_frame:
+            first8 = first.reshape(bsz, t).to(torch.bool).contiguous().view(torch.uint8)
+            qlo, _ = ops.episode_bounds(first8, None, maxlen, want_mask=False)       # once per call: the layers share it
         else:
             not_first = ~first[:, 0].reshape(bsz, 1, 1)
         state_out = []
@@ -564,6 +582,12 @@ class PolicyEngine:
                 att, kout, vout, m8 = ops.masked_attention_step(qkvr, kmem.contiguous(), vmem.contiguous(), state_mask.reshape(bsz, maxlen).contiguous(), first8,
                                                                w[p + "b_nd"], bsz, heads, hid, dtype=self.dtype, inplace=inplace_state, done=done)
                 new_mask = state_mask if inplace_state else m8.view(torch.bool).view(bsz, 1, maxlen)
+            elif per_frame:
+                mask8 = state_mask.reshape(bsz, maxlen).contiguous().view(torch.uint8)       # qlo covers first[:, 0]: the memory's own validity only
+                att = ops.masked_attention(qkvr, kmem.contiguous(), vmem.contiguous(), mask8, w[p + "b_nd"], bsz, t, heads, hid, dtype=self.dtype, qlo=qlo)
+                kout, vout = ops.kv_memory_update(qkvr, kmem.contiguous(), vmem.contiguous(), bsz, t, hid)
+                _, m8 = ops.episode_bounds(first8, mask8, maxlen, want_qlo=False)
+                new_mask = m8.view(torch.bool).view(bsz, 1, maxlen)
             else:
                 memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
                 att = ops.masked_attention(qkvr, kmem.contiguous(), vmem.contiguous(), memvalid, w[p + "b_nd"], bsz, t, heads, hid, dtype=self.dtype)

@@ -258,6 +258,20 @@ class MinecraftAgentPolicy(nn.Module):
         import os
         self._auto_graph = dict(enabled=os.environ.get("VPT_STEP_GRAPH", "1") != "0", batch=None, count=0)
         self._grad_engines = {}
+        self._episode_starts = "chunk"
+
+    @property
+    def episode_starts(self) -> str:
+        """"chunk" (default, the reference's single call: lib/masked_attention.py:167 reads first[:, 0]) or "frame" (set_episode_starts)."""
+        return self._episode_starts
+
+    def set_episode_starts(self, episode_starts: str):
+        """"frame": forward / get_output_for_observation / v, and the gradient-enabled path, honour first[b, t] at every t of a [B, T] call --
+        a chunk then computes what stepping its frames one at a time does (behavioural_cloning.py:95-112).  Acting (T = 1, the captured
+        step graph included) honours its one frame's `first` in either mode and is unchanged."""
+        from ..engine import check_episode_starts
+        self._episode_starts = check_episode_starts(episode_starts)
+        return self
 
     @property
     def precision(self) -> str:
@@ -529,7 +543,7 @@ class MinecraftAgentPolicy(nn.Module):
             if keep_pd:      # the next replay overwrites the graph's output buffers: what the caller may keep is copied
                 out["camera"], out["buttons"] = out["camera"].clone(), out["buttons"].clone()
         else:
-            out = self._engine.forward(img, first, state_in, mask=mask, sample=sample)
+            out = self._engine.forward(img, first, state_in, mask=mask, sample=sample, episode_starts=self._episode_starts)
         pi_logits = {"camera": out["camera"], "buttons": out["buttons"]}
         extra = {k: out[k] for k in ("action", "action_log_prob", "vpred_denorm", "nan_flag") if k in out}
         return (pi_logits, out["vpred"], None), out["state_out"], extra
@@ -543,6 +557,7 @@ class MinecraftAgentPolicy(nn.Module):
         eng = self._grad_engines.get(train_cnn)
         if eng is None:
             eng = self._grad_engines[train_cnn] = BCTrainer(self, train_cnn=train_cnn, optimizer_state=False)
+        eng.episode_starts = self._episode_starts
         names = [n for n, _ in named]
         out = _PolicyForwardFn.apply(self, eng, img, first, state_in, mask, names, *[p for _, p in named])
         lp_b, lp_c, vpred = out[:3]

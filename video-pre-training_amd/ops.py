@@ -520,12 +520,52 @@ def full_attention(qkv, batch, t, heads, hid, dtype=torch.bfloat16):
     return out
 
 
-def masked_attention(qkvr, kmem, vmem, memvalid, b_nd, batch, t, heads, hid, dtype=torch.bfloat16):
+def _chk_qlo(qlo, batch, t):
+    _chk(qlo, torch.int32, "qlo")
+    if qlo.numel() != batch * t:
+        raise ValueError(f"qlo must hold one int32 per frame ([{batch}, {t}]), got {tuple(qlo.shape)}")
+
+
+def episode_bounds(first, state_mask, maxlen, want_qlo=True, want_mask=True):
+    """Episode starts honoured at every frame (packing.episode_bounds on the device, vpt_episode_bounds_kernel).
+    first bool/uint8 [batch, t]; state_mask bool/uint8 [batch, maxlen] (needed for the mask only).
+    -> (qlo int32 [batch, t] | None, next state mask uint8 [batch, maxlen] | None)."""
+    if first.dtype == torch.bool:
+        first = first.view(torch.uint8)
+    _chk(first, torch.uint8, "first")
+    if first.dim() != 2 or first.shape[1] < 1:
+        raise ValueError(f"episode_bounds: first must be [batch, t >= 1], got {tuple(first.shape)}")
+    batch, t = first.shape
+    qlo = mout = None
+    if want_mask:
+        if state_mask is None:
+            raise ValueError("episode_bounds: the next mask needs state_mask")
+        if state_mask.dtype == torch.bool:
+            state_mask = state_mask.view(torch.uint8)
+        _chk(state_mask, torch.uint8, "state_mask")
+        if tuple(state_mask.shape) != (batch, maxlen):
+            raise ValueError(f"episode_bounds: state_mask must be [{batch}, {maxlen}], got {tuple(state_mask.shape)}")
+        mout = torch.empty_like(state_mask)
+    if want_qlo:
+        qlo = torch.empty(batch, t, dtype=torch.int32, device=first.device)
+    if batch and (want_qlo or want_mask):
+        _call("vpt_episode_bounds", dict(bytes=5.0 * batch * t + 2.0 * batch * maxlen), ptr(first), ptr(state_mask) if want_mask else None, ptr(qlo), ptr(mout),
+              batch, t, int(maxlen), _stream())
+    return qlo, mout
+
+
+def masked_attention(qkvr, kmem, vmem, memvalid, b_nd, batch, t, heads, hid, dtype=torch.bfloat16, qlo=None):
+    """qlo (int32 [batch, t], ops.episode_bounds): episode starts at any frame -- query i sees rows >= qlo[i] of [memory ; chunk] only."""
     _chk(qkvr, torch.float32, "qkvr"); _chk(kmem, torch.float32, "kmem"); _chk(vmem, torch.float32, "vmem")
     _chk(memvalid, torch.uint8, "memvalid"); _chk(b_nd, torch.float32, "b_nd")
     maxlen = kmem.shape[1]
     dt, fmt = _fmt(dtype=dtype)
     out = torch.empty(batch * t, hid, dtype=dt, device=qkvr.device)
+    if qlo is not None:
+        _chk_qlo(qlo, batch, t)
+        _call("vpt_masked_attention_forward_episodes", dict(flops=4.0 * batch * t * (t + maxlen) * hid), ptr(qkvr), ptr(kmem), ptr(vmem), ptr(memvalid), ptr(b_nd),
+              ptr(out), ptr(qlo), batch, t, heads, hid, qkvr.shape[1], maxlen, _stream(), fmt=fmt)
+        return out
     _call("vpt_masked_attention_forward", dict(flops=4.0 * batch * t * (t + maxlen) * hid), ptr(qkvr), ptr(kmem), ptr(vmem), ptr(memvalid), ptr(b_nd), ptr(out),
                  batch, t, heads, hid, qkvr.shape[1], maxlen, 1, _stream(), fmt=fmt)
     return out
@@ -763,13 +803,18 @@ def column_sum_(out, x_bf16, n):
     _call("vpt_column_sum", dict(bytes=2.0 * x_bf16.numel()), ptr(x_bf16), ptr(out), ptr(part), x_bf16.shape[0], n, x_bf16.shape[1], _stream(), fmt=_fmt(x_bf16)[1])
 
 
-def masked_attention_backward(qkvr, kmem, vmem, memvalid, b_nd, dout, db_nd, batch, t, heads, hid):
+def masked_attention_backward(qkvr, kmem, vmem, memvalid, b_nd, dout, db_nd, batch, t, heads, hid, qlo=None):
     for tt, nme in ((qkvr, "qkvr"), (kmem, "kmem"), (vmem, "vmem"), (b_nd, "b_nd"), (dout, "dout"), (db_nd, "db_nd")):
         _chk(tt, torch.float32, nme)
     _chk(memvalid, torch.uint8, "memvalid")
     dqkvr = torch.empty_like(qkvr) if qkvr.shape[1] == 3 * hid + 10 * heads else torch.zeros_like(qkvr)     # (every projection column is written)
     dkv = _workspace(WS_ATTENTION_BACKWARD_DKV, batch, t, hid, device=qkvr.device)
     dbnd = _workspace(WS_ATTENTION_BACKWARD_DBND, batch, t, heads, kmem.shape[1], device=qkvr.device)
+    if qlo is not None:     # the forward's episode bounds (ops.episode_bounds)
+        _chk_qlo(qlo, batch, t)
+        _call("vpt_masked_attention_backward_episodes", dict(flops=10.0 * batch * t * (t + kmem.shape[1]) * hid), ptr(qkvr), ptr(kmem), ptr(vmem),
+              ptr(memvalid), ptr(b_nd), ptr(dout), ptr(dqkvr), ptr(db_nd), ptr(dkv), ptr(dbnd), ptr(qlo), batch, t, heads, hid, qkvr.shape[1], kmem.shape[1], _stream())
+        return dqkvr
     _call("vpt_masked_attention_backward", dict(flops=10.0 * batch * t * (t + kmem.shape[1]) * hid), ptr(qkvr), ptr(kmem), ptr(vmem),
           ptr(memvalid), ptr(b_nd), ptr(dout), ptr(dqkvr), ptr(db_nd), ptr(dkv), ptr(dbnd), batch, t, heads, hid, qkvr.shape[1], kmem.shape[1], _stream())
     return dqkvr

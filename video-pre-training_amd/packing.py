@@ -148,3 +148,24 @@ def blocked_to_nchw(x_blocked, c, h, w):
 def nchw_to_blocked(x, dtype=torch.bfloat16):
     f, c, h, w = x.shape
     return x.view(f, c // 32, 32, h, w).permute(0, 1, 3, 4, 2).contiguous().to(dtype)
+
+
+def episode_bounds(first, state_mask, maxlen):
+    """Episode boundaries of a [B, t] chunk in the row coordinates of [memory (maxlen rows) ; chunk (t rows)] -- the host twin of
+    vpt_episode_bounds_kernel (ops.episode_bounds), for the attention mode that honours `first` at EVERY frame (what stepping the
+    reference one frame at a time computes, behavioural_cloning.py:95-112 over lib/masked_attention.py:161-178).
+    first bool [B, t]; state_mask bool [B, maxlen] (or [B, 1, maxlen], or None = nothing valid).  Returns
+      qlo int32 [B, t]: the lowest row query frame i may see = maxlen + (latest p <= i with first[b, p]), 0 when there is none;
+      next mask bool [B, maxlen]: kept row j = t + r is valid iff j >= qlo[b, t-1] and (j >= maxlen or state_mask[b, j])."""
+    bsz, t = first.shape
+    dev = first.device
+    first = first.to(torch.bool)
+    if state_mask is None:
+        state_mask = torch.zeros(bsz, maxlen, dtype=torch.bool, device=dev)
+    state_mask = state_mask.reshape(bsz, maxlen).to(torch.bool)
+    idx = torch.arange(t, device=dev).view(1, t).expand(bsz, t)
+    start = torch.where(first, idx, torch.full_like(idx, -1)).cummax(dim=1).values          # s(i), -1 = none
+    qlo = torch.where(start >= 0, start + maxlen, torch.zeros_like(start)).to(torch.int32)
+    rows = torch.cat([state_mask, torch.ones(bsz, t, dtype=torch.bool, device=dev)], dim=1)   # validity of every row of [memory ; chunk]
+    j = t + torch.arange(maxlen, device=dev).view(1, maxlen)
+    return qlo, rows[:, t:] & (j >= qlo[:, -1:])

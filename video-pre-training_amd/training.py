@@ -24,7 +24,7 @@ import torch.distributed as dist
 
 from . import distributed as D
 from . import ops, packing
-from .engine import DENSE_SPLITK
+from .engine import DENSE_SPLITK, check_episode_starts
 
 
 class _NullCtx:
@@ -64,8 +64,11 @@ def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], wei
 class BCTrainer:
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  train_cnn: bool = True, optimizer_state: bool = True, loss_scale: Optional[float] = None,
-                 scale_growth_interval: int = 200):
-        """train_cnn=True (default, as the reference: behavioural_cloning.py:57-63 optimises policy.parameters(), i.e. every
+                 scale_growth_interval: int = 200, episode_starts: str = "chunk"):
+        """episode_starts: "chunk" (default: first[:, 0] only) or "frame": `first` honoured at every frame of the chunk, forward and backward,
+        so that chunks cut from a stream of recordings of arbitrary length (sequence_batcher.SequenceBatcher) train as the reference's
+        frame-by-frame loop does (behavioural_cloning.py:95-112).
+        train_cnn=True (default, as the reference: behavioural_cloning.py:57-63 optimises policy.parameters(), i.e. every
         parameter) or False to freeze `net.img_process.cnn.*` and fine-tune trunk + heads only (no CNN activations kept).
         optimizer_state=False: gradients only (the autograd boundary of lib/policy.py), no Adam moments allocated.
 
@@ -77,6 +80,7 @@ class BCTrainer:
         torch.cuda.amp.GradScaler: vpt_grads_nonfinite_multi checks the (all-reduced) gradients; an overflowed step is skipped on
         the device (the Adam launch reads the flag) and the scale halves, it doubles after `scale_growth_interval` clean steps."""
         self.train_cnn = bool(train_cnn)
+        self.episode_starts = check_episode_starts(episode_starts)
         self.policy = policy
         self.engine = policy._engine
         self.dtype = self.engine.dtype
@@ -222,7 +226,13 @@ class BCTrainer:
         if cfg["use_pre_lstm_ln"]:     # MinecraftPolicy.pre_lstm_ln (lib/policy.py:202-203)
             x_pre = x
             x, _ = ops.layernorm(x_pre, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=dt)
-        not_first = ~first[:, 0].reshape(bsz, 1, 1)
+        per_frame = check_episode_starts(self.episode_starts) == "frame"
+        qlo = None
+        if per_frame:
+            first8 = first.reshape(bsz, t).to(torch.bool).contiguous().view(torch.uint8)
+            qlo, _ = ops.episode_bounds(first8, None, maxlen, want_mask=False)       # once per call: the layers (and their backward) share it
+        else:
+            not_first = ~first[:, 0].reshape(bsz, 1, 1)
         saved: List[dict] = []
         state_out = []
         for l in range(cfg["n_layers"]):
@@ -230,19 +240,26 @@ class BCTrainer:
             state_mask, (kmem, vmem) = state_in[l]
             if state_mask is None:
                 state_mask = torch.zeros(bsz, 1, maxlen, dtype=torch.bool, device=dev)
-            memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
+            if per_frame:
+                memvalid = state_mask.reshape(bsz, maxlen).to(torch.uint8).contiguous()          # qlo covers first[:, 0]
+            else:
+                memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
             kmem, vmem = kmem.contiguous(), vmem.contiguous()
             x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=dt)
             qkvr, _ = ops.linear(x1b, w[p + "qkvr.w"], eng.n_qkvr, bias=w[p + "qkvr.b"])
-            att = ops.masked_attention(qkvr, kmem, vmem, memvalid, w[p + "b_nd"], bsz, t, heads, hid, dtype=dt)
+            att = ops.masked_attention(qkvr, kmem, vmem, memvalid, w[p + "b_nd"], bsz, t, heads, hid, dtype=dt, qlo=qlo)
             kout, vout = ops.kv_memory_update(qkvr, kmem, vmem, bsz, t, hid)
             x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1)
             _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=dt)
             _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True)
             xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2)
-            saved.append(dict(x=x, x1b=x1b, qkvr=qkvr, kmem=kmem, vmem=vmem, memvalid=memvalid, att=att, x2=x2, hb=hb, h2=h2))
-            new_mask = torch.cat([state_mask[:, :, t:] & not_first,
-                                  torch.ones(bsz, 1, min(t, maxlen), dtype=torch.bool, device=dev)], dim=-1)
+            saved.append(dict(x=x, x1b=x1b, qkvr=qkvr, kmem=kmem, vmem=vmem, memvalid=memvalid, qlo=qlo, att=att, x2=x2, hb=hb, h2=h2))
+            if per_frame:
+                _, m8 = ops.episode_bounds(first8, memvalid, maxlen, want_qlo=False)
+                new_mask = m8.view(torch.bool).view(bsz, 1, maxlen)
+            else:
+                new_mask = torch.cat([state_mask[:, :, t:] & not_first,
+                                      torch.ones(bsz, 1, min(t, maxlen), dtype=torch.bool, device=dev)], dim=-1)
             state_out.append((new_mask, (kout, vout)))
             x = xo
         x_trunk = x
@@ -327,7 +344,7 @@ class BCTrainer:
             # attention
             g[o + "b_nd"] = torch.zeros(10, maxlen, dtype=torch.float32, device=dev)
             dqkvr = ops.masked_attention_backward(s["qkvr"], s["kmem"], s["vmem"], s["memvalid"], w[p + "b_nd"], datt,
-                                                  g[o + "b_nd"], bsz, t, heads, hid)
+                                                  g[o + "b_nd"], bsz, t, heads, hid, qlo=s["qlo"])
             nq = eng.n_qkvr
             dq16 = ops.gate_cast(dqkvr, _round_up(nq, 64), dtype=self.dtype)
             wq = torch.cat([P[o + "q_layer.weight"], P[o + "k_layer.weight"], P[o + "v_layer.weight"], P[o + "r_layer.weight"]], 0)
