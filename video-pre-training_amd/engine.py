@@ -11,6 +11,7 @@ KV memory fp32):
         -> layernorm -> linear(mlp0, relu) -> linear(mlp1,+res) ]
   layernorm(relu in) -> linear(lastlayer, relu) -> layernorm(final) -> linear(heads) -> log_softmax x2
 """
+import contextlib
 import os
 from typing import Dict, List, Optional
 
@@ -61,14 +62,6 @@ def check_supported(cfg: dict, idm: bool = False):
         raise NotImplementedError("hidsize must be a multiple of 256")
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
 PRECISIONS = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 
@@ -83,6 +76,37 @@ def check_episode_starts(episode_starts: str) -> str:
     return episode_starts
 
 
+class EpisodeMasks:
+    """The state-mask bookkeeping of a T > 1 call, one copy for PolicyEngine.forward and BCTrainer.forward_saving (the acting policy and the
+    trained one must see the same memories).  Built once per call: "frame" keeps first8 and the queries' lower bounds `qlo` (ops.episode_bounds:
+    the layers, and their backward, share them), "chunk" keeps `not_first` and qlo = None."""
+
+    def __init__(self, first, bsz: int, t: int, maxlen: int, episode_starts: str):
+        self.bsz, self.t, self.maxlen = bsz, t, maxlen
+        self.per_frame = check_episode_starts(episode_starts) == "frame"
+        self.qlo = None
+        if self.per_frame:
+            self.first8 = first8 = first.reshape(bsz, t).to(torch.bool).contiguous().view(torch.uint8)
+            self.qlo, _ = ops.episode_bounds(first8, None, maxlen, want_mask=False)
+        else:
+            self.not_first = ~first[:, 0].reshape(bsz, 1, 1)
+
+    def layer(self, state_mask, device):
+        """state_mask bool [B, 1, maxlen] | None -> (memvalid uint8 [B, maxlen]: the memory rows this call's queries may see,
+        new_mask bool [B, 1, maxlen]: the state mask that leaves the call)."""
+        bsz, t, maxlen = self.bsz, self.t, self.maxlen
+        if state_mask is None:
+            state_mask = torch.zeros(bsz, 1, maxlen, dtype=torch.bool, device=device)
+        if self.per_frame:
+            memvalid = state_mask.reshape(bsz, maxlen).to(torch.uint8).contiguous()       # qlo covers first[:, 0]: the memory's own validity only
+            _, m8 = ops.episode_bounds(self.first8, memvalid, maxlen, want_qlo=False)
+            return memvalid, m8.view(torch.bool).view(bsz, 1, maxlen)
+        not_first = self.not_first
+        memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
+        new_mask = torch.cat([state_mask[:, :, t:] & not_first, torch.ones(bsz, 1, min(t, maxlen), dtype=torch.bool, device=device)], dim=-1)
+        return memvalid, new_mask
+
+
 def resolve_precision(precision: Optional[str]) -> str:
     """precision=None -> env VPT_PRECISION -> "fp16", the parity mode (log-probs within the north star's 1e-3 of the fp32
     reference, exact actions outside a 10x narrower noise band).  "bf16" -- the north star's "MFMA bf16 tiles", what bench.py
@@ -91,6 +115,10 @@ def resolve_precision(precision: Optional[str]) -> str:
     if p not in PRECISIONS:
         raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {p!r}")
     return p
+
+
+def _f32(t):
+    return t.detach().float().contiguous()
 
 
 RNG_STREAM = {"buttons": 0, "camera": 1}     # which draw of a step a head takes from the in-kernel generator (ops.log_softmax_cols: rng)
@@ -151,19 +179,22 @@ class PolicyEngine:
     def __init__(self, cfg: dict, n_buttons: int, n_camera: int, cnn_chunk: int = 1024, cnn_streams: int = 3,
                  precision: Optional[str] = None):
         check_supported(cfg)
+        # pool_subchunk: frames per conv + pool sub-chunk of stacks 1.. (0: whole chunk).  Measured (profiles/r03_experiments.md section 12): 64 / 128 / 256
+        # frames all give +1.2 % on the forward step (the conv launches themselves run 1.8 % faster at 128 / 256); the pool kernel's own time does not move
+        self._init_common(cfg, precision, cnn_chunk=int(os.environ.get("VPT_CNN_CHUNK", cnn_chunk)), cnn_streams=int(os.environ.get("VPT_CNN_STREAMS", cnn_streams)),
+                          pool_subchunk=int(os.environ.get("VPT_POOL_SUBCHUNK", 256)), fuse_pool_sub=int(os.environ.get("VPT_FUSE_POOL_SUB", 0)))
+        self.n_buttons, self.n_camera = n_buttons, n_camera
+
+    def _init_common(self, cfg: dict, precision: Optional[str], cnn_chunk: int, cnn_streams: int, pool_subchunk: int, fuse_pool_sub: int):
+        """Every field the shared code reads, for both engines (IDMEngine names its own chunking instead of reading the VPT_CNN_* / VPT_*POOL_SUB* switches)."""
         self.precision = resolve_precision(precision)
         self.dtype = PRECISIONS[self.precision]
         self.cfg = cfg
-        self.n_buttons, self.n_camera = n_buttons, n_camera
-        self.cnn_chunk = int(os.environ.get("VPT_CNN_CHUNK", cnn_chunk))
-        self.cnn_streams = int(os.environ.get("VPT_CNN_STREAMS", cnn_streams))
-        # frames per conv + pool sub-chunk of stacks 1.. (0: whole chunk).  Measured (profiles/r03_experiments.md section 12): 64 / 128 / 256 frames
-        # all give +1.2 % on the forward step (the conv launches themselves run 1.8 % faster at 128 / 256); the pool kernel's own time does not move
-        self.pool_subchunk = int(os.environ.get("VPT_POOL_SUBCHUNK", 256))
+        self.cnn_chunk, self.cnn_streams, self.pool_subchunk = cnn_chunk, cnn_streams, pool_subchunk
         # stacks 1..: firstconv and the max-pool behind it as one pass (ops.conv3x3_pool); 0 = the two-kernel path above (A/B, and what the
         # latency tiling of the acting step always takes)
         self.fuse_pool = os.environ.get("VPT_FUSE_POOL", "1") != "0"
-        self.fuse_pool_sub = int(os.environ.get("VPT_FUSE_POOL_SUB", 0))      # frames per pool-fused launch (0: the whole chunk)
+        self.fuse_pool_sub = fuse_pool_sub                                             # frames per pool-fused launch (0: the whole chunk)
         # each stack's GroupNorm `n` folded into its first block (no affine pass; needs fuse_pool): 0 = the vpt_affine_kernel pass
         self.fold_n = os.environ.get("VPT_FOLD_N", "1") != "0"
         self.fold_stats_in_producer = os.environ.get("VPT_FOLD_STATS", "1") != "0"     # 0: per-channel sums by a pass of their own (A/B)
@@ -179,7 +210,6 @@ class PolicyEngine:
         self.w: Dict[str, torch.Tensor] = {}
         self.packed = False
 
-    step_overlap, _handoff = False, None      # class defaults (IDMEngine builds its own __init__; it never forks chunk streams)
     _RNG_MARK = 8        # how far the engine advances torch's CUDA generator offset when it derives a seed from it (see rng_state)
 
     def rng_state(self, device):
@@ -192,7 +222,7 @@ class PolicyEngine:
         BEFORE the engine's next stochastic call would go unnoticed: call seed() for that)."""
         cur = self._rng_state
         if cur is None or cur.device.type != device.type or (device.index is not None and cur.device.index != device.index):
-            pending = getattr(self, "_pending_seed", None)
+            pending = self._pending_seed
             self._rng_state = torch.zeros(2, dtype=torch.int64, device=device)
             self._rng_src = None
             if pending is not None:
@@ -227,67 +257,81 @@ class PolicyEngine:
 
     def adopt_sampler(self, other: "PolicyEngine"):
         """Take over another engine's sampler state (set_precision() builds a new engine: the seed and the step counter carry over)."""
-        self._rng_state, self._rng_src = other._rng_state, getattr(other, "_rng_src", None)
-        self._pending_seed = getattr(other, "_pending_seed", None)
+        self._rng_state, self._rng_src, self._pending_seed = other._rng_state, other._rng_src, other._pending_seed
 
     # ------------------------------------------------------------------------------------------
+    _QKV = "qkvr"        # the projections of a block's fused first linear, in row order (w[... + "qkvr.w"])
+
     @torch.no_grad()
     def pack(self, sd: Dict[str, torch.Tensor]):
         """Re-pack the fp32 state_dict (reference key names) for the kernels."""
-        cfg, w = self.cfg, {}
-        f32 = lambda t: t.detach().float().contiguous()
-        cin = 3
-        for s, c in enumerate(cfg["chans"]):
+        w = {}
+        self._pack_img_process(sd, w)
+        for l in range(self.cfg["n_layers"]):
+            self._pack_block(sd, w, l)
+        self._pack_trunk_norms(sd, w)
+        w["last.g"], w["last.b"] = _f32(sd["net.lastlayer.norm.weight"]), _f32(sd["net.lastlayer.norm.bias"])
+        w["last.w"] = ops.pack_linear(_f32(sd["net.lastlayer.layer.weight"]), dtype=self.dtype)
+        wh = torch.cat([_f32(sd["pi_head.buttons.linear_layer.weight"]), _f32(sd["pi_head.camera.linear_layer.weight"]),
+                        _f32(sd["value_head.linear.weight"])], dim=0)
+        bh = torch.cat([_f32(sd["pi_head.buttons.linear_layer.bias"]), _f32(sd["pi_head.camera.linear_layer.bias"]),
+                        _f32(sd["value_head.linear.bias"])])
+        w["heads.w"], w["heads.b"] = ops.pack_linear(wh, dtype=self.dtype), bh.contiguous()
+        self._packed(sd, w)
+
+    def _pack_conv(self, sd, q: str):
+        return ops.pack_conv3x3(_f32(sd[q + ".layer.weight"]), _f32(sd[q + ".norm.weight"]), _f32(sd[q + ".norm.bias"]), dtype=self.dtype)
+
+    def _pack_img_process(self, sd, w, normed_first: bool = False):
+        """ImgObsProcess: the IMPALA stacks, the dense layer and the linear behind it.  normed_first (IDM): stack 0's first conv is a normed
+        conv3x3 behind the temporal conv instead of the fused uint8 first conv."""
+        for s in range(len(self.cfg["chans"])):
             p = f"net.img_process.cnn.stacks.{s}."
-            if s == 0:
-                w[p + "firstconv"] = ops.pack_conv_first(f32(sd[p + "firstconv.layer.weight"]), f32(sd[p + "firstconv.layer.bias"]), dtype=self.dtype)
+            if s == 0 and not normed_first:
+                w[p + "firstconv"] = ops.pack_conv_first(_f32(sd[p + "firstconv.layer.weight"]), _f32(sd[p + "firstconv.layer.bias"]), dtype=self.dtype)
             else:
-                w[p + "firstconv"] = ops.pack_conv3x3(f32(sd[p + "firstconv.layer.weight"]), f32(sd[p + "firstconv.norm.weight"]), f32(sd[p + "firstconv.norm.bias"]), dtype=self.dtype)
-            w[p + "n.g"], w[p + "n.b"] = f32(sd[p + "n.weight"]), f32(sd[p + "n.bias"])
+                w[p + "firstconv"] = self._pack_conv(sd, p + "firstconv")
+            w[p + "n.g"], w[p + "n.b"] = _f32(sd[p + "n.weight"]), _f32(sd[p + "n.bias"])
             for b in range(2):
                 for cv in range(2):
-                    q = f"{p}blocks.{b}.conv{cv}"
-                    w[q] = ops.pack_conv3x3(f32(sd[q + ".layer.weight"]), f32(sd[q + ".norm.weight"]), f32(sd[q + ".norm.bias"]), dtype=self.dtype)
-            cin = c
-        c2 = cfg["chans"][-1]
+                    w[f"{p}blocks.{b}.conv{cv}"] = self._pack_conv(sd, f"{p}blocks.{b}.conv{cv}")
+        c2 = self.cfg["chans"][-1]
         p = "net.img_process.cnn.dense."
-        w[p + "g"] = ops.chw_to_blocked(f32(sd[p + "norm.weight"]), c2, 16, 16)
-        w[p + "b"] = ops.chw_to_blocked(f32(sd[p + "norm.bias"]), c2, 16, 16)
-        w[p + "w"] = ops.pack_linear(ops.chw_to_blocked(f32(sd[p + "layer.weight"]), c2, 16, 16), dtype=self.dtype)
+        w[p + "g"] = ops.chw_to_blocked(_f32(sd[p + "norm.weight"]), c2, 16, 16)
+        w[p + "b"] = ops.chw_to_blocked(_f32(sd[p + "norm.bias"]), c2, 16, 16)
+        w[p + "w"] = ops.pack_linear(ops.chw_to_blocked(_f32(sd[p + "layer.weight"]), c2, 16, 16), dtype=self.dtype)
         p = "net.img_process.linear."
-        w[p + "g"], w[p + "b"] = f32(sd[p + "norm.weight"]), f32(sd[p + "norm.bias"])
-        w[p + "w"] = ops.pack_linear(f32(sd[p + "layer.weight"]), dtype=self.dtype)
-        hid = cfg["hidsize"]
-        for l in range(cfg["n_layers"]):
-            p = f"net.recurrent_layer.blocks.{l}."
-            o = p + "r.orc_block."
-            w[p + "ln1.g"], w[p + "ln1.b"] = f32(sd[p + "pre_r_ln.weight"]), f32(sd[p + "pre_r_ln.bias"])
-            wq = torch.cat([f32(sd[o + "q_layer.weight"]), f32(sd[o + "k_layer.weight"]),
-                            f32(sd[o + "v_layer.weight"]), f32(sd[o + "r_layer.weight"])], dim=0)
-            nr = sd[o + "r_layer.weight"].shape[0]
-            bq = torch.cat([f32(sd[o + "q_layer.bias"]), torch.zeros(2 * hid, device=wq.device), f32(sd[o + "r_layer.bias"])])
-            w[p + "qkvr.w"], w[p + "qkvr.b"] = ops.pack_linear(wq, dtype=self.dtype), bq.contiguous()
-            w[p + "b_nd"] = f32(sd[o + "b_nd"])
-            w[p + "proj.w"], w[p + "proj.b"] = ops.pack_linear(f32(sd[o + "proj_layer.weight"]), dtype=self.dtype), f32(sd[o + "proj_layer.bias"])
-            w[p + "ln2.g"], w[p + "ln2.b"] = f32(sd[p + "mlp0.norm.weight"]), f32(sd[p + "mlp0.norm.bias"])
-            w[p + "mlp0.w"] = ops.pack_linear(f32(sd[p + "mlp0.layer.weight"]), dtype=self.dtype)
-            w[p + "mlp1.w"], w[p + "mlp1.b"] = ops.pack_linear(f32(sd[p + "mlp1.layer.weight"]), dtype=self.dtype), f32(sd[p + "mlp1.layer.bias"])
-            self.n_qkvr = 3 * hid + nr
-        if cfg["use_pre_lstm_ln"]:    # MinecraftPolicy.pre_lstm_ln (lib/policy.py:186-188,202-203): the reference's default, off in the released models
-            w["prelstm.g"], w["prelstm.b"] = f32(sd["net.pre_lstm_ln.weight"]), f32(sd["net.pre_lstm_ln.bias"])
-        w["last.g"], w["last.b"] = f32(sd["net.lastlayer.norm.weight"]), f32(sd["net.lastlayer.norm.bias"])
-        w["last.w"] = ops.pack_linear(f32(sd["net.lastlayer.layer.weight"]), dtype=self.dtype)
-        w["final.g"], w["final.b"] = f32(sd["net.final_ln.weight"]), f32(sd["net.final_ln.bias"])
-        wh = torch.cat([f32(sd["pi_head.buttons.linear_layer.weight"]), f32(sd["pi_head.camera.linear_layer.weight"]),
-                        f32(sd["value_head.linear.weight"])], dim=0)
-        bh = torch.cat([f32(sd["pi_head.buttons.linear_layer.bias"]), f32(sd["pi_head.camera.linear_layer.bias"]),
-                        f32(sd["value_head.linear.bias"])])
-        w["heads.w"], w["heads.b"] = ops.pack_linear(wh, dtype=self.dtype), bh.contiguous()
+        w[p + "g"], w[p + "b"] = _f32(sd[p + "norm.weight"]), _f32(sd[p + "norm.bias"])
+        w[p + "w"] = ops.pack_linear(_f32(sd[p + "layer.weight"]), dtype=self.dtype)
+
+    def _pack_block(self, sd, w, l: int):
+        """One transformer block; its first linear is the projections named by _QKV, concatenated (K and V have no bias: zero rows)."""
+        hid, qkv = self.cfg["hidsize"], self._QKV
+        p = f"net.recurrent_layer.blocks.{l}."
+        o = p + "r.orc_block."
+        w[p + "ln1.g"], w[p + "ln1.b"] = _f32(sd[p + "pre_r_ln.weight"]), _f32(sd[p + "pre_r_ln.bias"])
+        wq = torch.cat([_f32(sd[f"{o}{c}_layer.weight"]) for c in qkv], dim=0)
+        bq = torch.cat([_f32(sd[o + "q_layer.bias"]), torch.zeros(2 * hid, device=wq.device)] + [_f32(sd[f"{o}{c}_layer.bias"]) for c in qkv[3:]])
+        w[f"{p}{qkv}.w"], w[f"{p}{qkv}.b"] = ops.pack_linear(wq, dtype=self.dtype), bq.contiguous()
+        if "r" in qkv:
+            w[p + "b_nd"] = _f32(sd[o + "b_nd"])
+        w[p + "proj.w"], w[p + "proj.b"] = ops.pack_linear(_f32(sd[o + "proj_layer.weight"]), dtype=self.dtype), _f32(sd[o + "proj_layer.bias"])
+        w[p + "ln2.g"], w[p + "ln2.b"] = _f32(sd[p + "mlp0.norm.weight"]), _f32(sd[p + "mlp0.norm.bias"])
+        w[p + "mlp0.w"] = ops.pack_linear(_f32(sd[p + "mlp0.layer.weight"]), dtype=self.dtype)
+        w[p + "mlp1.w"], w[p + "mlp1.b"] = ops.pack_linear(_f32(sd[p + "mlp1.layer.weight"]), dtype=self.dtype), _f32(sd[p + "mlp1.layer.bias"])
+        self.n_qkvr = wq.shape[0]
+
+    def _pack_trunk_norms(self, sd, w):
+        if self.cfg["use_pre_lstm_ln"]:    # MinecraftPolicy.pre_lstm_ln (lib/policy.py:186-188,202-203): the reference's default, off in the released models
+            w["prelstm.g"], w["prelstm.b"] = _f32(sd["net.pre_lstm_ln.weight"]), _f32(sd["net.pre_lstm_ln.bias"])
+        w["final.g"], w["final.b"] = _f32(sd["net.final_ln.weight"]), _f32(sd["net.final_ln.bias"])
+
+    def _packed(self, sd, w):
         self.w = w
         self.packed = True
         # sources of the n-fold tables (computed on first use after a pack: inference only, nothing on the BC step's path)
         self._fold_src = {s: (sd[f"net.img_process.cnn.stacks.{s}.blocks.0.conv0.layer.weight"], sd[f"net.img_process.cnn.stacks.{s}.blocks.0.conv0.norm.weight"])
-                          for s in range(len(cfg["chans"]))}
+                          for s in range(len(self.cfg["chans"]))}
         self._dense_src = sd["net.img_process.cnn.dense.layer.weight"]
         self._fold_tab = {}
         self._handoff = None        # the next forward orders its chunk streams behind EVERYTHING on the calling stream (the packing kernels above)
@@ -467,7 +511,7 @@ class PolicyEngine:
         return ops.frame_affine(x, w[p + "g"], w[p + "b"], s_x, per_element=True)
 
     def _ln_linear(self, x, g, b, wpk, n, bias=None, res=None, relu=False, relu_in=False, ln_out_f32=False, out_f32=True, out_bf16=False,
-                   tiling="throughput"):
+                   tiling="throughput", splitk=1):
         """LayerNorm -> linear.  tiling "latency" (the acting step: <= 8 rows): ONE launch (the normalisation is a prologue of the
         weight-streaming kernel); "throughput": vpt_layernorm_kernel + the MFMA GEMM whatever the row count -- the CALLER's choice, never
         the row count's, so a row's result does not depend on the batch around it.
@@ -476,14 +520,31 @@ class PolicyEngine:
             return ops.layernorm_linear(x, g, b, wpk, n, bias=bias, res=res, relu=relu, relu_in=relu_in, ln_out_f32=ln_out_f32,
                                         out_f32=out_f32, out_bf16=out_bf16, dtype=self.dtype)
         ln32, ln16 = ops.layernorm(x, g, b, relu_in=relu_in, out_f32=ln_out_f32, dtype=self.dtype)
-        o32, o16 = ops.linear(ln16, wpk, n, bias=bias, res=res, relu=relu, out_f32=out_f32, out_bf16=out_bf16, tiling=tiling)
+        o32, o16 = ops.linear(ln16, wpk, n, bias=bias, res=res, relu=relu, out_f32=out_f32, out_bf16=out_bf16, tiling=tiling, splitk=splitk)
         return ln32, o32, o16
+
+    def _img_linear(self, d, tiling: str = "throughput", splitk=1) -> torch.Tensor:
+        """ImgObsProcess.linear over the CNN's pre-activation output (lib/policy.py:79-80): fp32 [N, 256] -> fp32 [N, hid]."""
+        w, p = self.w, "net.img_process.linear."
+        return self._ln_linear(d, w[p + "g"], w[p + "b"], w[p + "w"], self.cfg["hidsize"], relu=True, relu_in=True, tiling=tiling, splitk=splitk)[1]
+
+    def _block(self, x, l: int, tiling: str, splitk, attend) -> torch.Tensor:
+        """One transformer block of both engines (lib/xf.py): LN -> fused QKV(R) -> attend(qkv) -> proj + residual -> LN -> MLP + residual.
+        attend: fp32 [N, n_qkvr] -> the attention output, 16-bit [N, hid]."""
+        cfg, w = self.cfg, self.w
+        hid = cfg["hidsize"]
+        p = f"net.recurrent_layer.blocks.{l}."
+        x1, qkv, _ = self._ln_linear(x, w[p + "ln1.g"], w[p + "ln1.b"], w[f"{p}{self._QKV}.w"], self.n_qkvr, bias=w[f"{p}{self._QKV}.b"], ln_out_f32=True,
+                                     tiling=tiling, splitk=splitk)
+        x2, _ = ops.linear(attend(qkv), w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1, tiling=tiling, splitk=splitk)
+        _, _, h2 = self._ln_linear(x2, w[p + "ln2.g"], w[p + "ln2.b"], w[p + "mlp0.w"], hid * cfg["pointwise_ratio"], relu=True,
+                                   out_f32=False, out_bf16=True, tiling=tiling, splitk=splitk)
+        return ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, tiling=tiling, splitk=splitk)[0]
 
     def _img_process(self, frames: torch.Tensor, tiling: str = "throughput", frames_ready=None) -> torch.Tensor:
         """uint8 [N,128,128,3] -> fp32 [N,hid]  (ImgObsProcess.forward, lib/policy.py:79-80).  tiling: see ops.conv3x3.
         frames_ready: an event on the calling stream behind which `frames` is complete (forward() made a contiguous copy there); the pipelined
         chunk streams wait for it -- they do not wait for the calling stream itself."""
-        cfg, w = self.cfg, self.w
         n = frames.shape[0]
         outs = []
         n_chunks = (n + self.cnn_chunk - 1) // self.cnn_chunk
@@ -504,15 +565,13 @@ class PolicyEngine:
                 else:
                     st.wait_stream(main)
         for ci, i in enumerate(range(0, n, self.cnn_chunk)):
-            ctx = torch.cuda.stream(self._streams[ci % n_streams]) if n_streams > 1 else _NullCtx()
+            ctx = torch.cuda.stream(self._streams[ci % n_streams]) if n_streams > 1 else contextlib.nullcontext()
             with ctx:
                 outs.append(self._cnn_dense(frames[i:i + self.cnn_chunk], tiling=tiling))
         if n_streams > 1:
             for st in self._streams[:n_streams]:
                 main.wait_stream(st)
-        d = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-        p = "net.img_process.linear."
-        _, x, _ = self._ln_linear(d, w[p + "g"], w[p + "b"], w[p + "w"], cfg["hidsize"], relu=True, relu_in=True, tiling=tiling)
+        x = self._img_linear(outs[0] if len(outs) == 1 else torch.cat(outs, 0), tiling=tiling)
         if n_streams > 1 and self.step_overlap and not torch.cuda.is_current_stream_capturing():
             # the hand-off: every read of memory that belongs to the chunk streams' allocator pools (`outs`) is enqueued on `main` before this event,
             # so the next call's chunks may reuse it once the event has fired; everything behind it on `main` (transformer, heads) they do not wait for
@@ -554,51 +613,40 @@ class PolicyEngine:
         step = t == 1 and maxlen <= ops.ATTENTION_STEP_MAXLEN     # acting step: attention, memory shift and mask update in one launch
         if inplace_state and not step:
             raise ValueError("inplace_state is the acting step's option (T = 1)")
-        per_frame = episode_starts == "frame" and not step       # (the step kernel honours its one frame's `first` already)
-        if step:
+        if step:         # (the step kernel honours its one frame's `first` itself)
             first8 = first[:, 0].contiguous().view(torch.uint8)
-        elif per_frame:
-            first8 = first.reshape(bsz, t).to(torch.bool).contiguous().view(torch.uint8)
-            qlo, _ = ops.episode_bounds(first8, None, maxlen, want_mask=False)       # once per call: the layers share it
         else:
-            not_first = ~first[:, 0].reshape(bsz, 1, 1)
+            episodes = EpisodeMasks(first, bsz, t, maxlen, episode_starts)
         state_out = []
         for l in range(cfg["n_layers"]):
-            p = f"net.recurrent_layer.blocks.{l}."
             state_mask, (kmem, vmem) = state_in[l]
-            if state_mask is None:
-                state_mask = torch.zeros(bsz, 1, maxlen, dtype=torch.bool, device=x.device)
-            x1, qkvr, _ = self._ln_linear(x, w[p + "ln1.g"], w[p + "ln1.b"], w[p + "qkvr.w"], self.n_qkvr, bias=w[p + "qkvr.b"], ln_out_f32=True, tiling=tiling)
+            b_nd = w[f"net.recurrent_layer.blocks.{l}.b_nd"]
             if step:
-                if inplace_state and not (kmem.is_contiguous() and vmem.is_contiguous()):
-                    raise ValueError("inplace_state needs contiguous state tensors (a .contiguous() copy would receive the update instead of the state)")
+                if state_mask is None:
+                    state_mask = torch.zeros(bsz, 1, maxlen, dtype=torch.bool, device=x.device)
                 done = None
                 if inplace_state:       # the mask too: the last workgroup to arrive writes it (ops.masked_attention_step)
+                    if not (kmem.is_contiguous() and vmem.is_contiguous()):
+                        raise ValueError("inplace_state needs contiguous state tensors (a .contiguous() copy would receive the update instead of the state)")
                     if not state_mask.is_contiguous():
                         raise ValueError("inplace_state needs contiguous state masks")
                     if self._attn_done is None or self._attn_done.device != x.device:
                         self._attn_done = torch.zeros(64, dtype=torch.int32, device=x.device)
                     done = self._attn_done
-                att, kout, vout, m8 = ops.masked_attention_step(qkvr, kmem.contiguous(), vmem.contiguous(), state_mask.reshape(bsz, maxlen).contiguous(), first8,
-                                                               w[p + "b_nd"], bsz, heads, hid, dtype=self.dtype, inplace=inplace_state, done=done)
-                new_mask = state_mask if inplace_state else m8.view(torch.bool).view(bsz, 1, maxlen)
-            elif per_frame:
-                mask8 = state_mask.reshape(bsz, maxlen).contiguous().view(torch.uint8)       # qlo covers first[:, 0]: the memory's own validity only
-                att = ops.masked_attention(qkvr, kmem.contiguous(), vmem.contiguous(), mask8, w[p + "b_nd"], bsz, t, heads, hid, dtype=self.dtype, qlo=qlo)
-                kout, vout = ops.kv_memory_update(qkvr, kmem.contiguous(), vmem.contiguous(), bsz, t, hid)
-                _, m8 = ops.episode_bounds(first8, mask8, maxlen, want_qlo=False)
-                new_mask = m8.view(torch.bool).view(bsz, 1, maxlen)
+
+                def attend(qkvr):
+                    att, kout, vout, m8 = ops.masked_attention_step(qkvr, kmem.contiguous(), vmem.contiguous(), state_mask.reshape(bsz, maxlen).contiguous(), first8,
+                                                                   b_nd, bsz, heads, hid, dtype=self.dtype, inplace=inplace_state, done=done)
+                    state_out.append((state_mask if inplace_state else m8.view(torch.bool).view(bsz, 1, maxlen), (kout, vout)))
+                    return att
             else:
-                memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
-                att = ops.masked_attention(qkvr, kmem.contiguous(), vmem.contiguous(), memvalid, w[p + "b_nd"], bsz, t, heads, hid, dtype=self.dtype)
-                kout, vout = ops.kv_memory_update(qkvr, kmem.contiguous(), vmem.contiguous(), bsz, t, hid)
-                new_mask = torch.cat([state_mask[:, :, t:] & not_first,
-                                      torch.ones(bsz, 1, min(t, maxlen), dtype=torch.bool, device=x.device)], dim=-1)
-            x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1, tiling=tiling)
-            _, _, h2 = self._ln_linear(x2, w[p + "ln2.g"], w[p + "ln2.b"], w[p + "mlp0.w"], hid * cfg["pointwise_ratio"], relu=True,
-                                       out_f32=False, out_bf16=True, tiling=tiling)
-            x, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, tiling=tiling)
-            state_out.append((new_mask, (kout, vout)))
+                memvalid, new_mask = episodes.layer(state_mask, x.device)
+
+                def attend(qkvr):
+                    att = ops.masked_attention(qkvr, kmem.contiguous(), vmem.contiguous(), memvalid, b_nd, bsz, t, heads, hid, dtype=self.dtype, qlo=episodes.qlo)
+                    state_out.append((new_mask, ops.kv_memory_update(qkvr, kmem.contiguous(), vmem.contiguous(), bsz, t, hid)))
+                    return att
+            x = self._block(x, l, tiling, 1, attend)
 
         _, y, _ = self._ln_linear(x, w["last.g"], w["last.b"], w["last.w"], hid, relu=True, relu_in=True, tiling=tiling)
         nb, nc = self.n_buttons, self.n_camera
@@ -627,74 +675,29 @@ class IDMEngine(PolicyEngine):
     with a normed first conv, transformer blocks with mask "none" and no memory, ReLU, final_ln (the reference
     computes `lastlayer` and discards it, lib/policy.py:390-391 -- so it is not computed here), two heads."""
 
+    _QKV = "qkv"         # no R rows (lib/xf.py: the IDM's blocks have no relative-attention memory)
+
     def __init__(self, cfg: dict, button_shape, camera_shape, cnn_chunk: int = 128, precision: Optional[str] = None):
         check_supported(cfg, idm=True)
-        self.precision = resolve_precision(precision)
-        self.dtype = PRECISIONS[self.precision]
-        self.cfg = cfg
+        # (no chunk streams, no sub-chunks: the IDM's chunks are one 128-frame window)
+        self._init_common(cfg, precision, cnn_chunk=cnn_chunk, cnn_streams=1, pool_subchunk=0, fuse_pool_sub=0)
         self.button_shape, self.camera_shape = tuple(button_shape), tuple(camera_shape)  # (20, 2), (2, 11)
-        self.cnn_chunk = cnn_chunk
-        self.cnn_streams = 1
-        self.pool_subchunk = 0      # (PolicyEngine._cnn_chunk's option; the IDM's chunks are one 128-frame window)
-        self.fuse_pool = os.environ.get("VPT_FUSE_POOL", "1") != "0"
-        self.fuse_pool_sub = 0
-        self.fold_n = os.environ.get("VPT_FOLD_N", "1") != "0"
-        self.fold_stats_in_producer = os.environ.get("VPT_FOLD_STATS", "1") != "0"
-        self.fold_dense = os.environ.get("VPT_FOLD_DENSE", "1") != "0"
         # split-K of the trunk linears, named here (a function of the layer's (N, K) only, ops.nk_splitk) -- never chosen from the row count
         self.linear_splitk = "nk"
-        self._streams = []
-        self._rng_state = None
-        self._rng_src, self._pending_seed = None, None
-        self.w = {}
-        self.packed = False
 
     @torch.no_grad()
     def pack(self, sd):
-        cfg, w = self.cfg, {}
-        f32 = lambda t: t.detach().float().contiguous()
-        w["conv3d"] = ops.pack_conv3d_t5(f32(sd["net.conv3d_layer.layer.weight"]), f32(sd["net.conv3d_layer.layer.bias"]), dtype=self.dtype)
+        w = {}
+        w["conv3d"] = ops.pack_conv3d_t5(_f32(sd["net.conv3d_layer.layer.weight"]), _f32(sd["net.conv3d_layer.layer.bias"]), dtype=self.dtype)
         self.c3d_out = sd["net.conv3d_layer.layer.weight"].shape[0]
-        for s, c in enumerate(cfg["chans"]):
-            p = f"net.img_process.cnn.stacks.{s}."
-            w[p + "firstconv"] = ops.pack_conv3x3(f32(sd[p + "firstconv.layer.weight"]), f32(sd[p + "firstconv.norm.weight"]), f32(sd[p + "firstconv.norm.bias"]), dtype=self.dtype)
-            w[p + "n.g"], w[p + "n.b"] = f32(sd[p + "n.weight"]), f32(sd[p + "n.bias"])
-            for b in range(2):
-                for cv in range(2):
-                    q = f"{p}blocks.{b}.conv{cv}"
-                    w[q] = ops.pack_conv3x3(f32(sd[q + ".layer.weight"]), f32(sd[q + ".norm.weight"]), f32(sd[q + ".norm.bias"]), dtype=self.dtype)
-        c2 = cfg["chans"][-1]
-        p = "net.img_process.cnn.dense."
-        w[p + "g"] = ops.chw_to_blocked(f32(sd[p + "norm.weight"]), c2, 16, 16)
-        w[p + "b"] = ops.chw_to_blocked(f32(sd[p + "norm.bias"]), c2, 16, 16)
-        w[p + "w"] = ops.pack_linear(ops.chw_to_blocked(f32(sd[p + "layer.weight"]), c2, 16, 16), dtype=self.dtype)
-        p = "net.img_process.linear."
-        w[p + "g"], w[p + "b"] = f32(sd[p + "norm.weight"]), f32(sd[p + "norm.bias"])
-        w[p + "w"] = ops.pack_linear(f32(sd[p + "layer.weight"]), dtype=self.dtype)
-        hid = cfg["hidsize"]
-        for l in range(cfg["n_layers"]):
-            p = f"net.recurrent_layer.blocks.{l}."
-            o = p + "r.orc_block."
-            w[p + "ln1.g"], w[p + "ln1.b"] = f32(sd[p + "pre_r_ln.weight"]), f32(sd[p + "pre_r_ln.bias"])
-            wq = torch.cat([f32(sd[o + "q_layer.weight"]), f32(sd[o + "k_layer.weight"]), f32(sd[o + "v_layer.weight"])], dim=0)
-            bq = torch.cat([f32(sd[o + "q_layer.bias"]), torch.zeros(2 * hid, device=wq.device)])
-            w[p + "qkv.w"], w[p + "qkv.b"] = ops.pack_linear(wq, dtype=self.dtype), bq.contiguous()
-            w[p + "proj.w"], w[p + "proj.b"] = ops.pack_linear(f32(sd[o + "proj_layer.weight"]), dtype=self.dtype), f32(sd[o + "proj_layer.bias"])
-            w[p + "ln2.g"], w[p + "ln2.b"] = f32(sd[p + "mlp0.norm.weight"]), f32(sd[p + "mlp0.norm.bias"])
-            w[p + "mlp0.w"] = ops.pack_linear(f32(sd[p + "mlp0.layer.weight"]), dtype=self.dtype)
-            w[p + "mlp1.w"], w[p + "mlp1.b"] = ops.pack_linear(f32(sd[p + "mlp1.layer.weight"]), dtype=self.dtype), f32(sd[p + "mlp1.layer.bias"])
-        if cfg["use_pre_lstm_ln"]:
-            w["prelstm.g"], w["prelstm.b"] = f32(sd["net.pre_lstm_ln.weight"]), f32(sd["net.pre_lstm_ln.bias"])
-        w["final.g"], w["final.b"] = f32(sd["net.final_ln.weight"]), f32(sd["net.final_ln.bias"])
+        self._pack_img_process(sd, w, normed_first=True)
+        for l in range(self.cfg["n_layers"]):
+            self._pack_block(sd, w, l)
+        self._pack_trunk_norms(sd, w)
         for h in ("buttons", "camera"):
-            w[h + ".w"] = ops.pack_linear(f32(sd[f"pi_head.{h}.linear_layer.weight"]), dtype=self.dtype)
-            w[h + ".b"] = f32(sd[f"pi_head.{h}.linear_layer.bias"])
-        self.w = w
-        self.packed = True
-        self._fold_src = {s: (sd[f"net.img_process.cnn.stacks.{s}.blocks.0.conv0.layer.weight"], sd[f"net.img_process.cnn.stacks.{s}.blocks.0.conv0.norm.weight"])
-                          for s in range(len(cfg["chans"]))}
-        self._dense_src = sd["net.img_process.cnn.dense.layer.weight"]
-        self._fold_tab = {}
+            w[h + ".w"] = ops.pack_linear(_f32(sd[f"pi_head.{h}.linear_layer.weight"]), dtype=self.dtype)
+            w[h + ".b"] = _f32(sd[f"pi_head.{h}.linear_layer.bias"])
+        self._packed(sd, w)
 
     @torch.no_grad()
     def forward(self, img_u8: torch.Tensor, mask: Optional[dict] = None, sample: Optional[str] = None):
@@ -717,21 +720,11 @@ class IDMEngine(PolicyEngine):
             x0 = ops.conv3d_t5(fr, wfrag, bias, self.c3d_out, t, stats_out=s0)
             outs.append(self._cnn_dense(None, x0=x0, s_x0=s0))
             del x0
-        d = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-        p = "net.img_process.linear."
-        _, dn = ops.layernorm(d, w[p + "g"], w[p + "b"], relu_in=True, dtype=self.dtype)
-        x, _ = ops.linear(dn, w[p + "w"], hid, relu=True, tiling="throughput", splitk=sk)
+        x = self._img_linear(outs[0] if len(outs) == 1 else torch.cat(outs, 0), splitk=sk)
         if cfg["use_pre_lstm_ln"]:
             x, _ = ops.layernorm(x, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=self.dtype)
         for l in range(cfg["n_layers"]):
-            p = f"net.recurrent_layer.blocks.{l}."
-            x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=self.dtype)
-            qkv, _ = ops.linear(x1b, w[p + "qkv.w"], 3 * hid, bias=w[p + "qkv.b"], tiling="throughput", splitk=sk)
-            att = ops.full_attention(qkv, bsz, t, heads, hid, dtype=self.dtype)
-            x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1, tiling="throughput", splitk=sk)
-            _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=self.dtype)
-            _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * cfg["pointwise_ratio"], relu=True, out_f32=False, out_bf16=True, tiling="throughput", splitk=sk)
-            x, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, tiling="throughput", splitk=sk)
+            x = self._block(x, l, "throughput", sk, lambda qkv: ops.full_attention(qkv, bsz, t, heads, hid, dtype=self.dtype))
         latent, lb = ops.layernorm(x, w["final.g"], w["final.b"], relu_in=True, out_f32=True, dtype=self.dtype)
         out = {}
         temp = cfg["temperature"]

@@ -27,31 +27,27 @@ class KernelTimer:
     def reset(self):
         self.records = []
 
-    def summary(self):
+    def _accumulate(self, key_of):
+        """Sum the records under key_of(name, meta) (None: skip the record)."""
         torch.cuda.synchronize()
         out = {}
         for name, a, b, meta in self.records:
-            d = out.setdefault(name, dict(ms=0.0, calls=0, flops=0.0, bytes=0.0))
-            d["ms"] += a.elapsed_time(b)
-            d["calls"] += 1
-            d["flops"] += meta.get("flops", 0.0)
-            d["bytes"] += meta.get("bytes", 0.0)
-        return out
-
-    def by_shape(self, prefix="vpt_conv3x3"):
-        """Per (label, work size): the same records split by their FLOP / byte count, i.e. by layer shape (profiling: which shapes lose)."""
-        torch.cuda.synchronize()
-        out = {}
-        for name, a, b, meta in self.records:
-            if not name.startswith(prefix):
+            key = key_of(name, meta)
+            if key is None:
                 continue
-            key = (name, meta.get("flops", 0.0) or meta.get("bytes", 0.0))
             d = out.setdefault(key, dict(ms=0.0, calls=0, flops=0.0, bytes=0.0))
             d["ms"] += a.elapsed_time(b)
             d["calls"] += 1
             d["flops"] += meta.get("flops", 0.0)
             d["bytes"] += meta.get("bytes", 0.0)
         return out
+
+    def summary(self):
+        return self._accumulate(lambda name, meta: name)
+
+    def by_shape(self, prefix="vpt_conv3x3"):
+        """Per (label, work size): the same records split by their FLOP / byte count, i.e. by layer shape (profiling: which shapes lose)."""
+        return self._accumulate(lambda name, meta: (name, meta.get("flops", 0.0) or meta.get("bytes", 0.0)) if name.startswith(prefix) else None)
 
 
 TIMER = KernelTimer()
@@ -428,27 +424,24 @@ def linear(a_bf16, wpk, n, bias=None, res=None, relu=False, out_f32=True, out_bf
         tiles = ((m + 255) // 256) * ((n + 127) // 128)
         if tiles < 128:
             auto_sk = max(1, min(16, k // 512, 256 // tiles))
+    # the MFMA GEMM cuts K so that _every_split_has_k_steps tells whether every partial slice is written in full; the weight-streaming kernel cuts K its
+    # own way (and a split without k-steps writes nothing): keep its zero-fill
+    gemm = tl in (1, 4) or (tl == 0 and m > 8)
+    partials = lambda sk: (torch.empty if gemm and _every_split_has_k_steps(k, sk) else torch.zeros)(sk, m, n, dtype=torch.float32, device=dev)
+    o16 = None
+    if out_bf16:
+        o16 = torch.zeros(m, ld16, dtype=dt, device=dev) if ld16 > n else torch.empty(m, n, dtype=dt, device=dev)
     if auto_sk > 1:
-        part = (torch.empty if _every_split_has_k_steps(k, auto_sk) else torch.zeros)(auto_sk, m, n, dtype=torch.float32, device=dev)      # (this branch is always the MFMA GEMM)
+        part = partials(auto_sk)
         _call("vpt_linear_forward_tiled", dict(flops=2.0 * m * n * k, bytes=2.0 * (m * k + n * k) + 4.0 * m * n), ptr(a_bf16), ptr(wpk), None, None, ptr(part), None,
               m, n, k, k, n, n, n, 0, auto_sk, None, 0, tl, _stream(), fmt=fmt, label="vpt_linear_forward")
         o32 = torch.empty(m, n, dtype=torch.float32, device=dev) if out_f32 else None
-        o16 = None
-        if out_bf16:
-            o16 = torch.zeros(m, ld16, dtype=dt, device=dev) if ld16 > n else torch.empty(m, n, dtype=dt, device=dev)
         _call("vpt_linear_splitk_epilogue", dict(bytes=4.0 * (auto_sk + 1) * m * n), ptr(part), auto_sk, ptr(bias), ptr(res), ptr(o32), ptr(o16),
               m, n, n, n, ld16, 1 if relu else 0, ptr(mask), mask.shape[1] if mask is not None else 0, _stream(), fmt=fmt)
         return o32, o16
     o32 = None
-    if out_f32:   # split-K: one [m, n] slice per split (zeroed: a split without k-steps writes nothing), summed below
-        if splitk > 1:
-            gemm = tl in (1, 4) or (tl == 0 and m > 8)          # the MFMA GEMM's K partition (the weight-streaming kernel cuts K its own way: keep its zero-fill)
-            o32 = (torch.empty if gemm and _every_split_has_k_steps(k, splitk) else torch.zeros)(splitk, m, n, dtype=torch.float32, device=dev)
-        else:
-            o32 = torch.empty(m, n, dtype=torch.float32, device=dev)
-    o16 = None
-    if out_bf16:
-        o16 = torch.zeros(m, ld16, dtype=dt, device=dev) if ld16 > n else torch.empty(m, n, dtype=dt, device=dev)
+    if out_f32:   # split-K: one [m, n] slice per split, summed below
+        o32 = partials(splitk) if splitk > 1 else torch.empty(m, n, dtype=torch.float32, device=dev)
     _call("vpt_linear_forward_tiled", dict(flops=2.0 * m * n * k, bytes=2.0 * (m * k + n * k) + 4.0 * m * n), ptr(a_bf16), ptr(wpk), ptr(bias), ptr(res), ptr(o32), ptr(o16),
           m, n, k, k, n, n, ld16, 1 if relu else 0, splitk, ptr(mask), mask.shape[1] if mask is not None else 0, tl, _stream(), fmt=fmt, label="vpt_linear_forward")
     if splitk > 1 and o32 is not None and not splitk_raw:

@@ -16,6 +16,7 @@ fused first conv (vpt_conv_first_bwd_kernel).  train_cnn=False freezes `net.img_
 trunk and heads only (71 % of the 2x model's parameters).  Data parallelism: one process per GPU, sequences sharded by rank, the
 gradients summed over RCCL in buckets -- trunk + heads while the CNN backward runs, the CNN's at the end
 (BCTrainer.reduced_loss_and_grads); the 1 / global_frames factor is already in the loss gradient."""
+import contextlib
 import os
 from typing import Dict, List, Optional
 
@@ -24,15 +25,7 @@ import torch.distributed as dist
 
 from . import distributed as D
 from . import ops, packing
-from .engine import DENSE_SPLITK, check_episode_starts
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
+from .engine import DENSE_SPLITK, EpisodeMasks, check_episode_starts
 
 
 def _round_up(x: int, m: int) -> int:
@@ -205,7 +198,7 @@ class BCTrainer:
         outs, cnn_saved = [], []
         streams, main = self._chunk_streams((m + eng.cnn_chunk - 1) // eng.cnn_chunk)
         for ci, i in enumerate(range(0, m, eng.cnn_chunk)):
-            with (torch.cuda.stream(streams[ci % len(streams)]) if streams else _NullCtx()):
+            with (torch.cuda.stream(streams[ci % len(streams)]) if streams else contextlib.nullcontext()):
                 if self.train_cnn:
                     xn, sv = self._cnn_forward_saving(frames[i:i + eng.cnn_chunk])
                     cnn_saved.append(sv)
@@ -226,24 +219,14 @@ class BCTrainer:
         if cfg["use_pre_lstm_ln"]:     # MinecraftPolicy.pre_lstm_ln (lib/policy.py:202-203)
             x_pre = x
             x, _ = ops.layernorm(x_pre, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=dt)
-        per_frame = check_episode_starts(self.episode_starts) == "frame"
-        qlo = None
-        if per_frame:
-            first8 = first.reshape(bsz, t).to(torch.bool).contiguous().view(torch.uint8)
-            qlo, _ = ops.episode_bounds(first8, None, maxlen, want_mask=False)       # once per call: the layers (and their backward) share it
-        else:
-            not_first = ~first[:, 0].reshape(bsz, 1, 1)
+        episodes = EpisodeMasks(first, bsz, t, maxlen, self.episode_starts)      # the bookkeeping of PolicyEngine.forward: the same memories
+        qlo = episodes.qlo
         saved: List[dict] = []
         state_out = []
         for l in range(cfg["n_layers"]):
             p = f"net.recurrent_layer.blocks.{l}."
             state_mask, (kmem, vmem) = state_in[l]
-            if state_mask is None:
-                state_mask = torch.zeros(bsz, 1, maxlen, dtype=torch.bool, device=dev)
-            if per_frame:
-                memvalid = state_mask.reshape(bsz, maxlen).to(torch.uint8).contiguous()          # qlo covers first[:, 0]
-            else:
-                memvalid = (state_mask & not_first).reshape(bsz, maxlen).to(torch.uint8).contiguous()
+            memvalid, new_mask = episodes.layer(state_mask, dev)
             kmem, vmem = kmem.contiguous(), vmem.contiguous()
             x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=dt)
             qkvr, _ = ops.linear(x1b, w[p + "qkvr.w"], eng.n_qkvr, bias=w[p + "qkvr.b"])
@@ -254,12 +237,6 @@ class BCTrainer:
             _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True)
             xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2)
             saved.append(dict(x=x, x1b=x1b, qkvr=qkvr, kmem=kmem, vmem=vmem, memvalid=memvalid, qlo=qlo, att=att, x2=x2, hb=hb, h2=h2))
-            if per_frame:
-                _, m8 = ops.episode_bounds(first8, memvalid, maxlen, want_qlo=False)
-                new_mask = m8.view(torch.bool).view(bsz, 1, maxlen)
-            else:
-                new_mask = torch.cat([state_mask[:, :, t:] & not_first,
-                                      torch.ones(bsz, 1, min(t, maxlen), dtype=torch.bool, device=dev)], dim=-1)
             state_out.append((new_mask, (kout, vout)))
             x = xo
         x_trunk = x
@@ -376,7 +353,7 @@ class BCTrainer:
             accs = [acc] + [self._cnn_backward_accumulators(acc) for _ in range(n_acc - 1)]     # operands shared, accumulators per stream
             streams, main = self._chunk_streams(len(cnn_saved))                                   # (after the zero-fills above were enqueued)
             for ci, i in enumerate(range(0, m, eng.cnn_chunk)):
-                with (torch.cuda.stream(streams[ci % len(streams)]) if streams else _NullCtx()):
+                with (torch.cuda.stream(streams[ci % len(streams)]) if streams else contextlib.nullcontext()):
                     self._cnn_backward_chunk(cnn_saved[ci], dd[i:i + eng.cnn_chunk].contiguous(), accs[ci % len(accs)])
                     cnn_saved[ci] = None
             for st in streams:
@@ -506,13 +483,9 @@ class BCTrainer:
     def _conv_layer_backward(self, q, acc, dy, y, res, x_in, s_in, skip, need_dx=True, pool=None):
         """One GN -> conv3x3 -> ReLU (+res) layer: accumulates the raw weight-gradient pieces and returns dx (+skip).
         pool = (dpooled, argmax) when the layer feeds the stack's max-pool (dy is then None)."""
-        w = self.engine.w
-        _, sa, sg = w[q]
+        _, sa, sg = self.engine.w[q]
         cin = x_in.shape[1] * 32
-        n = cin * x_in.shape[2] * x_in.shape[3]
-        r = acc["raw"].get(q)
-        if r is None:   # [dw_raw, d_sa, d_sg]: the kernels accumulate into them across the frame chunks
-            r = acc["raw"][q] = [torch.zeros(y.shape[1] * 32, 9, cin, dtype=torch.float32, device=y.device), torch.zeros_like(sa), torch.zeros_like(sg)]
+        r = self._raw_acc(acc, q, y.shape[1] * 32, cin, sa, sg)
         dacc, coef, _, _ = ops.conv_backward_prepare(dy, y, res, s_in, sa, sg, cin, dpooled=pool[0] if pool else None,
                                                      argmax=pool[1] if pool else None, d_sa=r[1], d_sg=r[2])
         ops.conv3x3_wgrad(dacc, x_in, out=r[0])
