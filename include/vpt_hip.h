@@ -80,9 +80,11 @@ int vpt_chw_to_blocked(const float* src, float* dst, int64_t rows, int C, int H,
  *   VPT_WS_ATTENTION_BACKWARD_DBND (B, t, heads, maxlen, -)  ... and its dbnd_slab
  *   VPT_WS_FRAME_AFFINE_BACKWARD (frames, HW, per_element, pass, C)   vpt_frame_affine_backward's partials for that pass
  *   VPT_WS_CONV_FIRST_BACKWARD   (frames, H, W, -, Cout)     vpt_conv_first_backward's partials (depends on the device's CU count)
+ *   VPT_WS_BC_LOSS               (M, -, -, -, -)             vpt_bc_loss's workspace (the record slab + its reduction scratch)
  * Returns -1 for an unknown op. */
 enum { VPT_WS_CONV3X3_WGRAD = 1, VPT_WS_CONV_BACKWARD_PREPARE = 2, VPT_WS_LINEAR_SPLITK = 3, VPT_WS_LAYERNORM_BACKWARD = 4, VPT_WS_COLUMN_SUM = 5,
-       VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9 };
+       VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9,
+       VPT_WS_BC_LOSS = 10 };
 int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout);
 int vpt_pack_conv3x3(const float* weight, const float* gain, const float* bias, void* wpk, float* edge_sa, float* edge_sg,
                      int Cout, int Cin, void* stream);
@@ -335,6 +337,22 @@ int vpt_grads_nonfinite_multi(const void* table, int ntensors, int64_t total_blo
  * bf16 [M][ldz] (columns >= nb+nc zero): scale = 1 / (global frames * temperature).  lib/action_head.py:170-184. */
 int vpt_bc_nll_backward(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons,
                         const int64_t* act_camera, void* dz, int M, int nb, int nc, int ldz, float scale, void* stream);
+
+/* The BC loss with per-frame weights, its gradient and its metrics in one sweep over the log-probs:
+ *   loss = sum_rows w (nll_b + nll_c) / sum_rows w   (behavioural_cloning.py:107 with w = 1; padding / left-out frames: w = 0),
+ * plus what lib/action_head.py:176-193 offers per head -- logprob of the label, entropy -- and the arg-max hit.  Every output is optional (NULL):
+ *   dz        16-bit [M][ldz], ldz >= nb + nc: (exp(lp) - onehot) * (scale * weight[row]), further columns zero -- vpt_bc_nll_backward's values at the
+ *             row's own scale, bit for bit; the caller folds 1 / (sum w * temperature) (and the fp16 loss scale) into `scale`;
+ *   frame_out fp32 [M][8]: nll_buttons, nll_camera, entropy_buttons, entropy_camera (-sum p lp, a term with p = 0 counts 0), hit_buttons, hit_camera
+ *             (1 = the head's arg-max is the label; ties: lowest index), w, 0 -- the frame's own, unweighted values;
+ *   totals    fp32 [8]: sum_rows w * frame_out[row][k] for k < 6, sum w, the number of rows with w > 0.  The rows' records are added in a fixed order
+ *             through `workspace` (vpt_workspace_bytes(VPT_WS_BC_LOSS, M, ...) bytes, required with totals; M <= 65536): no atomics, the same inputs give the
+ *             same bits.
+ * weight fp32 [M] or NULL (all ones).  A row with weight 0 stores exact zeros in dz and adds exact zeros to totals whatever its log-probs hold (NaN
+ * included); labels are only compared with column indices, so an out-of-range label (a padded frame's) reads nothing and matches nothing. */
+int vpt_bc_loss(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons, const int64_t* act_camera,
+                const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
+                int M, int nb, int nc, int ldz, float scale, void* stream);
 
 /* The same boundary for an ARBITRARY incoming gradient -- what torch autograd hands to the outputs of
  * MinecraftAgentPolicy.forward / get_output_for_observation (lib/policy.py:252-305) when the caller writes its own loss, as

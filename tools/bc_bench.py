@@ -1,5 +1,5 @@
 """Time the BC step (forward + backward + Adam) on one GPU and print the per-kernel breakdown.
-python tools/bc_bench.py [--model 2x] [--batch 64] [--seq 128] [--steps 2] [--no-cnn]"""
+python tools/bc_bench.py [--model 2x] [--batch 64] [--seq 128] [--steps 2] [--no-cnn] [--weights]"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="2x"); ap.add_argument("--batch", type=int, default=64); ap.add_argument("--seq", type=int, default=128)
 ap.add_argument("--steps", type=int, default=2); ap.add_argument("--no-cnn", action="store_true")
 ap.add_argument("--streams1", action="store_true", help="the instrumented step on ONE stream (per-kernel durations without cross-stream overlap, as bench.py reports them)")
+ap.add_argument("--weights", action="store_true", help="every step with frame_weight=ones and metrics={}: the loss path through vpt_bc_loss_kernel")
 a = ap.parse_args()
 dev = "cuda"
 pk = configs.policy_kwargs_for(a.model)
@@ -32,12 +33,13 @@ img = torch.randint(0, 256, (B, T, 128, 128, 3), generator=g, dtype=torch.uint8)
 first = torch.zeros(B, T, dtype=torch.bool, device=dev)
 ab = torch.randint(0, 8641, (B, T), generator=g).to(dev); ac = torch.randint(0, 121, (B, T), generator=g).to(dev)
 st = pol.initial_state(B)
-loss, st = tr.step(img, first, st, ab, ac)
+kw = (lambda: dict(frame_weight=torch.ones(B, T, device=dev), metrics={})) if a.weights else dict
+loss, st = tr.step(img, first, st, ab, ac, **kw())
 torch.cuda.synchronize()
 print("warm-up loss", loss, "peak mem GB", torch.cuda.max_memory_allocated() / 2**30)
 t0 = time.perf_counter()
 for _ in range(a.steps):
-    loss, st = tr.step(img, first, st, ab, ac)
+    loss, st = tr.step(img, first, st, ab, ac, **kw())
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.steps
 print(f"BC step {dt*1e3:.1f} ms  ({B*T/dt:.0f} frames/s)  loss {loss:.4f}")
@@ -45,7 +47,7 @@ if a.streams1:
     tr.cnn_streams = 1
 ops.TIMER.enabled = True; ops.TIMER.reset()
 t0 = time.perf_counter()
-tr.step(img, first, st, ab, ac)
+tr.step(img, first, st, ab, ac, **kw())
 torch.cuda.synchronize()
 print(f"instrumented step wall {1e3*(time.perf_counter()-t0):.1f} ms")
 summ = ops.TIMER.summary()

@@ -5,6 +5,8 @@
 // reuse vpt_gemm_kernel (dgrad with W^T packed, wgrad with A = dY^T); this file holds the rest:
 //
 //  vpt_nll_bwd_kernel    : d/dz of -(log_softmax(z/T)[a]) summed over the two heads -> bf16 dz (GEMM operand).
+//  vpt_bc_loss_kernel    : the same gradient with per-frame weights, plus per-head NLL / entropy / arg-max hit per frame and their weighted
+//                          totals (one sweep; the totals through a slab row per frame + vpt_slab_sum: bit-reproducible).
 //  vpt_ln_bwd_kernel     : nn.LayerNorm backward (optionally through a ReLU on its input), dgain/dbias by
 //                          per-workgroup register partials -> the workgroup's row of a partial slab -> vpt_ln_bwd_finish_kernel
 //                          (fixed summation order: bit-reproducible).
@@ -37,6 +39,107 @@ extern "C" int vpt_nll_bwd_launch(const VptNllBwdArgs* a, hipStream_t stream) {
   if (a->M <= 0 || a->ldz < a->nb + a->nc) return -1;
   hipLaunchKernelGGL(vpt_nll_bwd_kernel, dim3(a->M), dim3(256), 0, stream, *a);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The BC loss with per-frame weights and its metrics in ONE sweep over a frame's nb + nc log-probs (behavioural_cloning.py:107,
+// lib/action_head.py:176-193): every element is loaded once and feeds the loss gradient dz, the label's log-prob, the entropy sum and the arg-max.
+//   loss = sum_rows w (nll_b + nll_c) / sum_rows w;  the caller folds 1 / (sum w x temperature) into `scale`, the row's factor is scale * w.
+// A row with w == 0 (padding, a frame left out of the loss) stores exact zeros in dz and in its slab record whatever its log-probs hold, and its
+// labels are only ever COMPARED with the sweep index (the label's log-prob is picked up where i == label), never used as one.
+// One element of dz, in vpt_nll_bwd_kernel's order of operations -- (exp(lp) - onehot) * row_scale, no contraction -- so that a weighted row equals,
+// bit for bit, that kernel's row at scale' = scale * w.
+__device__ __forceinline__ float bc_loss_grad(float p, bool is_label, float row_scale) {
+#pragma clang fp contract(off)
+  const float d = p - (is_label ? 1.f : 0.f);
+  return d * row_scale;
+}
+
+__global__ __launch_bounds__(256) void vpt_bc_loss_kernel(VptBcLossArgs a) {
+  __shared__ float red[4][6];
+  __shared__ int redi[4][2];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float* lb = a.lp_buttons + (size_t)row * a.nb;
+  const float* lc = a.lp_camera + (size_t)row * a.nc;
+  const float w = a.weight ? a.weight[row] : 1.f;
+  const bool live = w != 0.f;
+  const float rs = a.scale * w;
+  const long ab64 = a.act_buttons[row], ac64 = a.act_camera[row];
+  const int ab = (ab64 >= 0 && ab64 < a.nb) ? (int)ab64 : -1, ac = (ac64 >= 0 && ac64 < a.nc) ? (int)ac64 : -1;   // out of range: matches no element
+  const bool stats = a.frame_out || a.slab;
+  vpt_op16* dz = a.dz ? a.dz + (size_t)row * a.ldz : nullptr;
+  const int nbc = a.nb + a.nc, n = dz ? a.ldz : nbc;
+  float eb = 0.f, ec = 0.f, pb = 0.f, pc = 0.f;            // sum p lp and the label's lp, per head
+  float mb = -INFINITY, mc = -INFINITY;                    // running arg-max, per head
+  int ib = 0x7fffffff, ic = 0x7fffffff;
+  for (int i = tid; i < n; i += 256) {
+    float g = 0.f;
+    if (i < a.nb) {
+      const float l = lb[i], p = expf(l);
+      g = bc_loss_grad(p, i == ab, rs);
+      eb += (p == 0.f) ? 0.f : p * l;
+      if (i == ab) pb += l;
+      argmax_take(mb, ib, l, i);
+    } else if (i < nbc) {
+      const int j = i - a.nb;
+      const float l = lc[j], p = expf(l);
+      g = bc_loss_grad(p, j == ac, rs);
+      ec += (p == 0.f) ? 0.f : p * l;
+      if (j == ac) pc += l;
+      argmax_take(mc, ic, l, j);
+    }
+    if (dz) dz[i] = (vpt_op16)(live ? g : 0.f);
+  }
+  if (!stats) return;
+  eb = wave_sum(eb); ec = wave_sum(ec); pb = wave_sum(pb); pc = wave_sum(pc);
+  wave_argmax(mb, ib); wave_argmax(mc, ic);
+  const int wv = tid >> 6;
+  if ((tid & 63) == 0) {
+    red[wv][0] = eb; red[wv][1] = ec; red[wv][2] = pb; red[wv][3] = pc; red[wv][4] = mb; red[wv][5] = mc;
+    redi[wv][0] = ib; redi[wv][1] = ic;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  float s[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+  int best[2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float v01 = red[0][4 + h], v23 = red[2][4 + h];
+    int i01 = redi[0][h], i23 = redi[2][h];
+    argmax_take(v01, i01, red[1][4 + h], redi[1][h]);
+    argmax_take(v23, i23, red[3][4 + h], redi[3][h]);
+    argmax_take(v01, i01, v23, i23);
+    best[h] = i01;
+  }
+  // [nll_b, nll_c, ent_b, ent_c, hit_b, hit_c, w, 0]: the frame's own (unweighted) values
+  const float rec[8] = {-s[2], -s[3], -s[0], -s[1], (ab >= 0 && best[0] == ab) ? 1.f : 0.f, (ac >= 0 && best[1] == ac) ? 1.f : 0.f, w, 0.f};
+  if (a.frame_out) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a.frame_out[(size_t)row * 8 + k] = rec[k];
+  }
+  if (a.slab) {    // the weighted record: row `row` of the [M][8] slab vpt_slab_sum adds in its fixed order (slot 6: w, slot 7: one per row with w > 0)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.slab[(size_t)row * 8 + k] = live ? w * rec[k] : 0.f;
+    a.slab[(size_t)row * 8 + 6] = live ? w : 0.f;
+    a.slab[(size_t)row * 8 + 7] = (w > 0.f) ? 1.f : 0.f;
+  }
+}
+
+extern "C" long vpt_bc_loss_workspace_floats(int M) { return M > 0 ? 8L * M + vpt_slab_sum_scratch_floats(M, 8) : 0; }
+
+extern "C" int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* workspace, hipStream_t stream) {
+  if (a->M <= 0 || a->nb <= 0 || a->nc <= 0) return -1;
+  if (a->dz && a->ldz < a->nb + a->nc) return -1;
+  if (totals && !workspace) return -1;
+  if (totals && a->M > 65536) return -2;        // vpt_slab_sum: at most 256 slices of 256 rows
+  VptBcLossArgs k = *a;
+  k.slab = totals ? workspace : nullptr;
+  hipLaunchKernelGGL(vpt_bc_loss_kernel, dim3(a->M), dim3(256), 0, stream, k);
+  if (hipGetLastError() != hipSuccess) return -3;
+  if (!totals) return 0;
+  return vpt_slab_sum_launch(workspace, a->M, 8, 8L, totals, 8, nullptr, 0, workspace + 8L * a->M, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

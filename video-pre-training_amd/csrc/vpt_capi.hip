@@ -79,6 +79,7 @@ int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout)
     case VPT_WS_ATTENTION_BACKWARD_DBND: return 4 * (int64_t)vpt_attn_bwd_dbnd_floats(frames, H, W, Cin);   /* (B, t, heads, maxlen) */
     case VPT_WS_FRAME_AFFINE_BACKWARD: return 4 * (int64_t)vpt_affine_bwd_partial_floats(frames, Cout / 32, H, W, Cin);   /* (frames, HW, per_element, pass, C) */
     case VPT_WS_CONV_FIRST_BACKWARD: return 4 * (int64_t)vpt_conv_first_bwd_partial_floats(frames, H, W, Cout);
+    case VPT_WS_BC_LOSS: return 4 * (int64_t)vpt_bc_loss_workspace_floats(frames);                          /* (M) */
     case VPT_WS_LINEAR_SPLITK: return 4 * (int64_t)frames * H * (int64_t)W;   /* splitk (= frames) x M (= H) x N (= W) fp32 partial slices */
     default: return -1;
   }
@@ -526,6 +527,19 @@ int vpt_bc_nll_backward(const float* lp_buttons, const float* lp_camera, const i
   a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.act_buttons = (const long*)act_buttons;
   a.act_camera = (const long*)act_camera; a.dz = (vpt_op16*)dz; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz; a.scale = scale;
   CHECK_LAUNCH(vpt_nll_bwd_launch(&a, (hipStream_t)stream), "vpt_bc_nll_backward");
+}
+
+int vpt_bc_loss(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons, const int64_t* act_camera,
+                const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
+                int M, int nb, int nc, int ldz, float scale, void* stream) {
+  if (!lp_buttons || !lp_camera || !act_buttons || !act_camera) return fail(-1, "vpt_bc_loss: null log-probs / labels");
+  if (M <= 0) return fail(-1, "vpt_bc_loss: M must be positive");
+  if (dz && ldz < nb + nc) return fail(-1, "vpt_bc_loss: ldz < nb + nc");
+  if (totals && !workspace) return fail(-1, "vpt_bc_loss: totals need the workspace (VPT_WS_BC_LOSS)");
+  VptBcLossArgs a = {};
+  a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.act_buttons = (const long*)act_buttons; a.act_camera = (const long*)act_camera;
+  a.weight = weight; a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz; a.scale = scale;
+  CHECK_LAUNCH(vpt_bc_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_bc_loss");
 }
 
 int vpt_heads_logprob_backward(const float* lp_buttons, const float* lp_camera, const float* g_buttons, const float* g_camera,

@@ -117,6 +117,19 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// arg-max as (value, index) pairs: the larger value wins, on equal values the lower index (torch.argmax's choice); a NaN never wins
+__device__ __forceinline__ void argmax_take(float& bv, int& bi, float v, int i) {
+  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+__device__ __forceinline__ void wave_argmax(float& bv, int& bi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    argmax_take(bv, bi, ov, oi);
+  }
+}
+
 // per-frame statistics -> (mean, rstd).  stats[2f] = sum, stats[2f+1] = sum of squares (double)
 __device__ __forceinline__ void frame_mean_rstd(const double* __restrict__ stats, int f, double inv_count,
                                                 float& mean, float& rstd) {

@@ -295,6 +295,19 @@ struct VptNllBwdArgs {
   float scale;             // 1 / (frames in the global batch * temperature)
 };
 
+struct VptBcLossArgs {      // weighted BC loss: gradient + per-frame records + totals in one sweep (vpt_bc_loss_kernel)
+  const float* lp_buttons; // [M][nb] log-probabilities (forward output)
+  const float* lp_camera;  // [M][nc]
+  const long* act_buttons; // [M]; only compared with column indices (an out-of-range label matches nothing)
+  const long* act_camera;  // [M]
+  const float* weight;     // optional [M] per-frame weights (null: all ones); a row with weight 0 writes exact zeros to dz and to its slab record
+  vpt_op16* dz;            // optional [M][ldz]: (exp(lp) - onehot) * (scale * weight[row]), columns nb+nc.. zero
+  float* frame_out;        // optional [M][8]: nll_b, nll_c, ent_b, ent_c, hit_b, hit_c, w, 0 (unweighted)
+  float* slab;             // set by the launcher: [M][8] weighted records, summed by vpt_slab_sum into the totals
+  int M, nb, nc, ldz;
+  float scale;
+};
+
 struct VptHeadsBwdArgs {   // generic backward of the two log-softmax heads + the value column (autograd boundary)
   const float* lp_buttons; // [M][nb] log-probabilities (forward output)
   const float* lp_camera;  // [M][nc]
@@ -410,6 +423,8 @@ int vpt_conv_wgrad_launch(const VptConvWgradArgs* a, hipStream_t s);
 int vpt_pack_conv3x3_launch(const VptPackConvArgs* a, hipStream_t s);
 int vpt_pack_linear_launch(const float* w, void* out, int N, int K, int transposed, int ldw, int src_rows, hipStream_t s);
 int vpt_nll_bwd_launch(const VptNllBwdArgs* a, hipStream_t s);
+long vpt_bc_loss_workspace_floats(int M);
+int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* workspace, hipStream_t s);
 int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);
 int vpt_ln_bwd_launch(const VptLnBwdArgs* a, hipStream_t s);
 int vpt_gate_cast_launch(const VptGateCastArgs* a, hipStream_t s);

@@ -70,7 +70,7 @@ def _call(name, meta, *args, fmt="bf16", label=None):
 
 
 WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
-WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD = 6, 7, 8, 9
+WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
 
 
 def _workspace(op, a=0, b=0, c=0, d=0, e=0, device=None, fmt="bf16"):
@@ -750,6 +750,29 @@ def nll_backward(lp_buttons, lp_camera, act_buttons, act_camera, ldz, scale, dty
     _call("vpt_bc_nll_backward", dict(bytes=6.0 * m * ldz), ptr(lp_buttons), ptr(lp_camera), ptr(act_buttons), ptr(act_camera),
           ptr(dz), m, nb, nc, ldz, ctypes.c_float(scale), _stream(), fmt=fmt)
     return dz
+
+
+def bc_loss(lp_buttons, lp_camera, act_buttons, act_camera, ldz, scale, weight=None, dtype=torch.bfloat16, want_dz=True, want_frames=True,
+            want_totals=True):
+    """The weighted BC loss in one sweep over the log-probs (vpt_bc_loss) -> (dz | None, frame_out | None, totals | None).
+    dz: 16-bit [M, ldz], nll_backward's values with row r at scale * weight[r] (a zero-weight row: exact zeros); frame_out fp32 [M, 8] =
+    nll_b, nll_c, ent_b, ent_c, hit_b, hit_c, w, 0 per frame (unweighted); totals fp32 [8] = sum_r w frame_out[r, :6], sum w, rows with w > 0.
+    weight: fp32 [M] or None (all ones).  packing.bc_loss_metrics is the host twin of frame_out / totals."""
+    _chk(lp_buttons, torch.float32, "lp_buttons"); _chk(lp_camera, torch.float32, "lp_camera")
+    _chk(act_buttons, torch.int64, "act_buttons"); _chk(act_camera, torch.int64, "act_camera"); _chk(weight, torch.float32, "weight")
+    m, nb = lp_buttons.shape
+    nc = lp_camera.shape[1]
+    if lp_camera.shape[0] != m or act_buttons.numel() != m or act_camera.numel() != m or (weight is not None and weight.numel() != m):
+        raise ValueError(f"bc_loss: every per-frame tensor must have {m} rows")
+    dt, fmt = _fmt(dtype=dtype)
+    dev = lp_buttons.device
+    dz = torch.empty(m, ldz, dtype=dt, device=dev) if want_dz else None
+    frame_out = torch.empty(m, 8, dtype=torch.float32, device=dev) if want_frames else None
+    totals = torch.empty(8, dtype=torch.float32, device=dev) if want_totals else None
+    ws = _workspace(WS_BC_LOSS, m, device=dev, fmt=fmt) if want_totals else None
+    _call("vpt_bc_loss", dict(bytes=(4.0 * (nb + nc) + (2.0 * ldz if want_dz else 0.0)) * m), ptr(lp_buttons), ptr(lp_camera), ptr(act_buttons),
+          ptr(act_camera), ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws), m, nb, nc, ldz, ctypes.c_float(scale), _stream(), fmt=fmt)
+    return dz, frame_out, totals
 
 
 def heads_logprob_backward(lp_buttons, lp_camera, g_buttons, g_camera, g_value, ldz, temperature, mask_buttons=None, mask_camera=None,

@@ -169,3 +169,30 @@ def episode_bounds(first, state_mask, maxlen):
     rows = torch.cat([state_mask, torch.ones(bsz, t, dtype=torch.bool, device=dev)], dim=1)   # validity of every row of [memory ; chunk]
     j = t + torch.arange(maxlen, device=dev).view(1, maxlen)
     return qlo, rows[:, t:] & (j >= qlo[:, -1:])
+
+
+def bc_loss_metrics(lp_buttons, lp_camera, act_buttons, act_camera, weight=None):
+    """Per-frame records and totals of the weighted BC loss -- the host twin of vpt_bc_loss_kernel (ops.bc_loss), in fp64 torch; the
+    formulas of lib/action_head.py:176-193 (logprob of the label, entropy) and behavioural_cloning.py:107 (their negated sum is the loss).
+    lp_* [M, n] log-probs; act_* int [M]; weight [M] or None (all ones).  Returns
+      frame_out fp64 [M, 8]: nll_b, nll_c, ent_b, ent_c, hit_b, hit_c, w, 0 -- the frame's own (unweighted) values; an entropy term with
+                 p == 0 counts 0, a hit is `arg-max (lowest index on ties) == label`, a label outside [0, n) picks nothing (nll 0, no hit);
+      totals fp64 [8]: sum_rows w * frame_out[row, :6], sum w, number of rows with w > 0; a row with w == 0 adds exact zeros whatever it holds."""
+    m = lp_buttons.shape[0]
+    dev = lp_buttons.device
+    w = torch.ones(m, dtype=torch.float64, device=dev) if weight is None else weight.reshape(m).to(torch.float64)
+    cols = []
+    for lp, act in ((lp_buttons, act_buttons), (lp_camera, act_camera)):
+        lp = lp.to(torch.float64)
+        act = act.reshape(m, 1).to(torch.int64)
+        onehot = torch.arange(lp.shape[1], device=dev).view(1, -1) == act
+        nll = -torch.where(onehot, lp, torch.zeros_like(lp)).sum(-1)
+        p = lp.exp()
+        ent = -torch.where(p == 0, torch.zeros_like(lp), p * lp).sum(-1)
+        hit = (lp.argmax(-1, keepdim=True) == act).reshape(m).to(torch.float64)
+        cols.append((nll, ent, hit))
+    frame_out = torch.stack([cols[0][0], cols[1][0], cols[0][1], cols[1][1], cols[0][2], cols[1][2], w, torch.zeros_like(w)], dim=1)
+    live = (w != 0).view(m, 1)
+    rec = torch.where(live, w.view(m, 1) * frame_out[:, :6], torch.zeros_like(frame_out[:, :6]))
+    totals = torch.cat([rec.sum(0), torch.where(live.view(m), w, torch.zeros_like(w)).sum().view(1), (w > 0).sum().to(torch.float64).view(1)])
+    return frame_out, totals

@@ -46,15 +46,21 @@ class SequenceBatcher:
 
     action_encoder: callable list[dict] -> (buttons [N], camera [N]) (tensors or arrays); default: default_action_encoder on the
     loader's device.  Iteration ends when any lane cannot supply its T items (the reference stops at the first empty lane,
-    data_loader.py:198-217); the incomplete chunk is dropped and its items are counted in `dropped_frames`."""
+    data_loader.py:198-217); the incomplete chunk is dropped and its items are counted in `dropped_frames`.
 
-    def __init__(self, loader, seq_len: int, action_encoder: Optional[Callable] = None):
+    pad_last=True keeps that chunk instead: every chunk also carries `weight` fp32 [B, T] (BCTrainer's `frame_weight`; all ones for a full
+    chunk), and when a lane runs dry the chunk in progress is completed with padding -- zero image, first = True, action indices 0,
+    episode_id = -1, weight = 0 -- and returned if it holds at least one real item; the next iteration stops.  `dropped_frames` stays 0, and
+    only real items reach the action encoder."""
+
+    def __init__(self, loader, seq_len: int, action_encoder: Optional[Callable] = None, pad_last: bool = False):
         if int(seq_len) < 1:
             raise ValueError("seq_len must be at least 1")
         if getattr(loader, "to_numpy", False):
             raise ValueError("SequenceBatcher needs the loader's frames as tensors (to_numpy=False)")
         self.loader = loader
         self.seq_len = int(seq_len)
+        self.pad_last = bool(pad_last)
         self.n_rows = loader.n_workers
         self.device = torch.device(loader._device)
         self._encode = action_encoder or default_action_encoder(self.device)
@@ -77,9 +83,18 @@ class SequenceBatcher:
                 item = self.loader.next_lane_item(b)
                 if item is None:
                     self._done = True
+                    if self.pad_last and any(rows):
+                        return self._padded_chunk(rows)
                     self.dropped_frames += sum(len(r) for r in rows)
                     raise StopIteration()
                 rows[b].append(item)
+        chunk = self._chunk(rows)
+        if self.pad_last:
+            chunk["weight"] = torch.ones(self.n_rows, self.seq_len, dtype=torch.float32, device=self.device)
+        return chunk
+
+    def _chunk(self, rows):
+        """A full chunk from `rows` (T items per lane)."""
         bsz, t = self.n_rows, self.seq_len
         ids = torch.tensor([[it[0] for it in r] for r in rows], dtype=torch.int64)
         prev = torch.tensor([[-1 if p is None else p] for p in self._last_id], dtype=torch.int64)
@@ -93,3 +108,27 @@ class SequenceBatcher:
         to_bt = lambda x: torch.as_tensor(x).to(device=self.device, dtype=torch.int64).reshape(bsz, t)
         self.n_chunks += 1
         return dict(img=img, first=first.to(self.device), act_buttons=to_bt(buttons), act_camera=to_bt(camera), episode_id=ids.to(self.device))
+
+    def _padded_chunk(self, rows):
+        """The last, incomplete chunk (pad_last): the real items of every lane followed by padding."""
+        bsz, t = self.n_rows, self.seq_len
+        ids = torch.full((bsz, t), -1, dtype=torch.int64)
+        first = torch.ones(bsz, t, dtype=torch.bool)
+        weight = torch.zeros(bsz, t, dtype=torch.float32)
+        img = torch.zeros(bsz, t, 128, 128, 3, dtype=torch.uint8, device=self.device)
+        for b, r in enumerate(rows):
+            prev = self._last_id[b]
+            for i, it in enumerate(r):
+                ids[b, i], first[b, i], weight[b, i] = it[0], prev is None or it[0] != prev, 1.0
+                img[b, i] = torch.as_tensor(it[1]).to(self.device)
+                prev = it[0]
+            self._last_id[b] = prev
+        real = weight.reshape(-1) > 0
+        acts = torch.zeros(2, bsz * t, dtype=torch.int64, device=self.device)
+        buttons, camera = self._encode([it[2] for r in rows for it in r])        # real items only, in lane order
+        where = real.to(self.device)
+        acts[0, where] = torch.as_tensor(buttons).to(device=self.device, dtype=torch.int64).reshape(-1)
+        acts[1, where] = torch.as_tensor(camera).to(device=self.device, dtype=torch.int64).reshape(-1)
+        self.n_chunks += 1
+        return dict(img=img, first=first.to(self.device), act_buttons=acts[0].view(bsz, t), act_camera=acts[1].view(bsz, t),
+                    episode_id=ids.to(self.device), weight=weight.to(self.device))

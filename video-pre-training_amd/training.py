@@ -146,10 +146,19 @@ class BCTrainer:
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, global_frames: Optional[int] = None, debug: Optional[dict] = None,
-                       on_trunk_grads=None, unscaled: bool = True):
+    def loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, global_frames: Optional[float] = None, debug: Optional[dict] = None,
+                       on_trunk_grads=None, unscaled: bool = True, *, frame_weight=None, metrics: Optional[dict] = None, _weight_sum=None):
         """Forward (saving activations) + backward.  Returns (loss of this rank's frames, grads dict, state_out).
-        global_frames: number of frames in the global (all-rank) batch the mean runs over (default: local).
+        global_frames: number of frames in the global (all-rank) batch the mean runs over (default: local); with frame_weight the global
+        weight sum (it may then be a float).
+        frame_weight: [B, T] finite, non-negative per-frame weights: loss = sum w nll / sum w and its gradient (0 = padding or a frame left out:
+        whatever its image and labels hold, it adds exact zeros); sum w and min w are read on the host before anything is queued (one transfer) --
+        ValueError on a negative or non-finite weight, and on sum w == 0 unless global_frames says other ranks carry weight.
+        metrics: a dict this call fills (as `debug`): loss, nll_buttons, nll_camera, acc_buttons, acc_camera, entropy_buttons, entropy_camera
+        (weighted means, lib/action_head.py:176-193), weight_sum, frames (rows with w > 0), frame_nll fp32 [B, T], frame_out fp32 [B, T, 8]
+        (ops.bc_loss's records) -- device tensors, nothing synchronises.  With neither, the loss path is ops.nll_backward + a gather, as ever;
+        otherwise ONE ops.bc_loss launch writes dz, the per-frame records the returned loss is formed from (_record_loss) and the totals behind the
+        metrics and the reduction over ranks.
         unscaled=True: the gradients of the mean loss in both operand formats.  False (what step() uses): in the fp16 mode they are
         left multiplied by 1 / grad_unscale(global_frames) -- the optimiser launch folds that factor in, no extra pass.
         on_trunk_grads(g): called once the gradients of everything behind the CNN (88 % of the parameters) are final and
@@ -158,16 +167,29 @@ class BCTrainer:
             # the callback (an asynchronous all-reduce in the data-parallel step) would see loss-SCALED gradients that this function then
             # multiplies in place while the collective may still be reading them
             raise ValueError("loss_and_grads: on_trunk_grads needs unscaled=False in the fp16 (loss-scaled) mode; apply grad_unscale() after the exchange")
+        w, wsum = None, None
+        if frame_weight is not None:
+            w, wsum = (frame_weight, _weight_sum) if _weight_sum is not None else self._checked_weights(frame_weight, img_u8)
+            if not global_frames and wsum == 0:
+                raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
         S = self.forward_saving(img_u8, first, state_in)
         m = S["m"]
         ab = act_buttons.reshape(m).to(torch.int64).contiguous()
         ac = act_camera.reshape(m).to(torch.int64).contiguous()
-        loss = -(S["lp_b"].gather(1, ab[:, None]) + S["lp_c"].gather(1, ac[:, None])).mean()
-        gf = global_frames or m
+        gf = global_frames or (m if w is None else wsum)
         # bf16: the gradient of the global mean.  fp16: loss_scale x the gradient of the SUM over frames (see __init__); grad_unscale()
         # is the factor that turns the returned gradients into those of the mean.
         scale = (self.loss_scale if self.scaled else 1.0 / gf) / self.engine.cfg["temperature"]
-        dz = ops.nll_backward(S["lp_b"], S["lp_c"], ab, ac, S["ldz"], scale, dtype=self.dtype)
+        if w is None and metrics is None:
+            loss = -(S["lp_b"].gather(1, ab[:, None]) + S["lp_c"].gather(1, ac[:, None])).mean()
+            dz = ops.nll_backward(S["lp_b"], S["lp_c"], ab, ac, S["ldz"], scale, dtype=self.dtype)
+        else:       # one sweep over the log-probs: dz, the per-frame records and their fixed-order totals
+            dz, frame_out, totals = ops.bc_loss(S["lp_b"], S["lp_c"], ab, ac, S["ldz"], scale, weight=w, dtype=self.dtype)
+            loss = self._record_loss(frame_out, w, wsum)        # this rank's; NaN where its shard carries no weight (reduced_loss_and_grads sums the totals)
+            self._bc_totals = totals
+            if metrics is not None:
+                self._fill_metrics(metrics, totals, frame_out, S["bsz"], S["t"])
+                metrics["loss"] = loss
         g = self.backward_from(S, dz, on_trunk_grads=on_trunk_grads, debug=debug)
         if unscaled and self.scaled:
             f = self.grad_unscale(gf)
@@ -175,9 +197,70 @@ class BCTrainer:
                 t_.mul_(f)
         return loss, g, S["state_out"]
 
-    def grad_unscale(self, global_frames: int) -> float:
-        """What loss_and_grads' gradients must be multiplied by to be d(mean loss)/d(parameter): 1 in bf16."""
+    def grad_unscale(self, global_frames: float) -> float:
+        """What loss_and_grads' gradients must be multiplied by to be d(mean loss)/d(parameter): 1 in bf16.  (global_frames: the global weight
+        sum when the step carries frame weights.)"""
         return 1.0 / (self.loss_scale * global_frames) if self.scaled else 1.0
+
+    @staticmethod
+    def _checked_weights(frame_weight, img_u8):
+        """[B, T] weights -> (fp32 [M] on the images' device, their fp64 sum as a host float).  The sum and the minimum come to the host in ONE
+        transfer; a negative or non-finite weight raises ValueError (a NaN makes the minimum NaN, an infinity the sum infinite)."""
+        m = img_u8.shape[0] * img_u8.shape[1]
+        w = torch.as_tensor(frame_weight)
+        if w.numel() != m:
+            raise ValueError(f"frame_weight must hold one weight per frame ([{img_u8.shape[0]}, {img_u8.shape[1]}]), got {tuple(w.shape)}")
+        w = w.reshape(m).to(device=img_u8.device, dtype=torch.float32).contiguous()
+        w64 = w.to(torch.float64)
+        wsum, wmin = torch.stack([w64.sum(), w64.min()]).tolist()
+        if not (wmin >= 0.0) or wsum != wsum or wsum in (float("inf"), float("-inf")):
+            raise ValueError(f"frame_weight must be finite and non-negative (min {wmin}, sum {wsum})")
+        return w, wsum
+
+    @staticmethod
+    def _record_loss(frame_out, w, wsum):
+        """sum w nll / sum w of one rank from the kernel's per-frame records, in the ARITHMETIC OF THE DEFAULT PATH: per frame nll_b + nll_c (the
+        negated sum of the two picked log-probs, exactly), then torch's mean over the frames, then the factor M / sum w.  With every weight 1 each
+        step is the default path's own -- w x is x, the mean of the negated values is the negated mean, the factor is 1.0 -- so frame_weight=ones (and
+        metrics={} alone) returns the default path's loss bit for bit; the totals' fixed tree adds the same terms in another association and lands an
+        ulp away, which is why the returned loss is not read from them (they feed the metrics and the reduction over ranks).  M floats per step."""
+        nll = frame_out[:, 0] + frame_out[:, 1]
+        if w is None:
+            return nll.mean()
+        wn = torch.where(w != 0, w * nll, torch.zeros_like(nll))          # a zero-weight frame counts an exact zero whatever its record holds
+        return wn.mean() * (nll.numel() / wsum if wsum else float("nan"))
+
+    @staticmethod
+    def _fill_metrics(metrics: dict, totals, frame_out, bsz: int, t: int):
+        """totals [8] (ops.bc_loss's, or their sum over ranks) + this rank's records -> the metrics dict; device arithmetic only."""
+        ws = totals[6]
+        metrics.update(loss=(totals[0] + totals[1]) / ws, nll_buttons=totals[0] / ws, nll_camera=totals[1] / ws,
+                       entropy_buttons=totals[2] / ws, entropy_camera=totals[3] / ws, acc_buttons=totals[4] / ws, acc_camera=totals[5] / ws,
+                       weight_sum=ws, frames=totals[7])
+        if frame_out is not None:
+            metrics.update(frame_nll=(frame_out[:, 0] + frame_out[:, 1]).view(bsz, t), frame_out=frame_out.view(bsz, t, 8))
+
+    @torch.no_grad()
+    def evaluate(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None):
+        """Forward-only loss and metrics of a [B, T] chunk -> (metrics dict as loss_and_grads fills it, state_out).  The inference forward
+        (PolicyEngine.forward, nothing saved) + ops.bc_loss without dz: no activations, no optimiser state (works with optimizer_state=False)."""
+        w = None
+        if frame_weight is not None:
+            w, wsum = self._checked_weights(frame_weight, img_u8)
+            if wsum == 0:
+                raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
+        self.policy._ensure_packed()
+        eng = self.engine
+        bsz, t = img_u8.shape[:2]
+        m = bsz * t
+        out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
+        lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
+        ab = act_buttons.reshape(m).to(torch.int64).contiguous()
+        ac = act_camera.reshape(m).to(torch.int64).contiguous()
+        _, frame_out, totals = ops.bc_loss(lp_b, lp_c, ab, ac, 0, 0.0, weight=w, dtype=self.dtype, want_dz=False)
+        metrics: dict = {}
+        self._fill_metrics(metrics, totals, frame_out, bsz, t)
+        return metrics, out["state_out"]
 
     @torch.no_grad()
     def forward_saving(self, img_u8, first, state_in, mask: Optional[dict] = None) -> dict:
@@ -599,8 +682,11 @@ class BCTrainer:
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def reduced_loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera):
+    def reduced_loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None):
         """This rank's shard of the batch -> (global mean loss, gradients of the GLOBAL mean loss summed over ranks, state_out).
+        frame_weight / metrics: as loss_and_grads.  With weights the count the ranks agree on is sum_ranks sum w (fp64), the loss is
+        sum_ranks(sum w nll) / that, and a rank whose shard carries no weight is legal while the global sum is positive; requested metrics
+        are GLOBAL (the eight totals travel in the final reduction, next to the health flag); frame_nll / frame_out are this rank's frames.
         (fp16 mode: the gradients stay loss-scaled, i.e. are those of the mean divided by grad_unscale(global frames); step() hands
         that factor to the optimiser launch.)
         The loss gradient already carries 1 / global_frames, so the exchange is a plain sum, in two bucketed all-reduces:
@@ -615,14 +701,35 @@ class BCTrainer:
         # force_exchange (VPT_DP_FORCE_EXCHANGE=1): take the data-parallel path in a ONE-rank group too -- the frame-count reduction, both arenas, the early exchange
         # under the CNN backward, the late one, the health reduction -- so that the whole step can be run (and timed) over the real transport on a 1-GPU box
         force = bool(getattr(self, "force_exchange", False)) and dist.is_initialized()
+        fused = frame_weight is not None or metrics is not None      # the loss path through ops.bc_loss (its totals), else the unchanged default
         if world == 1 and not force:
-            return self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=m_local, unscaled=False)
+            if not fused:
+                return self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=m_local, unscaled=False)
+            w, wsum = self._checked_weights(frame_weight, img_u8) if frame_weight is not None else (None, None)
+            if wsum is not None:
+                if wsum == 0:
+                    raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
+                self._global_frames = wsum
+            return self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=self._global_frames, unscaled=False,
+                                       frame_weight=w, metrics=metrics, _weight_sum=wsum)
         dev = img_u8.device
         # Shards may differ by one sequence when B % world != 0 (distributed.shard_range): the mean runs over the TRUE global
-        # frame count, and the reported loss is the frame-weighted mean of the ranks' losses.
-        count = torch.tensor([float(m_local)], dtype=torch.float64, device=dev)
+        # frame count, and the reported loss is the frame-weighted mean of the ranks' losses.  With frame weights the count is the global weight sum;
+        # a rank whose weights are invalid still joins every collective (with zeros) and reports itself in the final reduction.
+        err, w, wsum = None, None, None
+        if frame_weight is not None:
+            try:
+                w, wsum = self._checked_weights(frame_weight, img_u8)
+            except ValueError as e:
+                err, wsum = e, 0.0
+        count = torch.tensor([float(m_local) if frame_weight is None else wsum], dtype=torch.float64, device=dev)
         dist.all_reduce(count)
-        m_global = self._global_frames = int(round(float(count.item())))
+        if frame_weight is None:
+            m_global = self._global_frames = int(round(float(count.item())))
+        else:
+            m_global = self._global_frames = float(count.item())
+            if err is None and m_global == 0:
+                err = ValueError("frame_weight: every weight of the global batch is zero (the loss sum w nll / sum w is undefined)")
         early = [n for n in self.trainable if not n.startswith("net.img_process.cnn.")]   # final before the CNN backward
         late = [n for n in self.trainable if n.startswith("net.img_process.cnn.")]
         pending, state = [], dict(early_sent=False)
@@ -638,10 +745,18 @@ class BCTrainer:
             pending.extend(arena_early.all_reduce_start(force))
             state["early_sent"] = True
 
-        err, loss, grads, state_out = None, None, None, None
+        loss, grads, state_out = None, None, None
+        local_metrics = {} if metrics is not None else None
         try:
-            loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera,
-                                                         global_frames=m_global, on_trunk_grads=start_trunk_exchange, unscaled=False)
+            if err is not None:
+                raise err
+            if fused:
+                loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=m_global,
+                                                             on_trunk_grads=start_trunk_exchange, unscaled=False, frame_weight=w,
+                                                             metrics=local_metrics, _weight_sum=wsum)
+            else:
+                loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera,
+                                                             global_frames=m_global, on_trunk_grads=start_trunk_exchange, unscaled=False)
             arena_late.adopt(grads)
             pending.extend(arena_late.all_reduce_start(force))
         except Exception as e:          # e.g. out of memory on this rank: still take part in every collective (with zeros of
@@ -652,6 +767,19 @@ class BCTrainer:
             arena_late.flat.zero_()
             pending.extend(arena_late.all_reduce_start(force))
         D.bucketed_all_reduce_finish(pending)
+        if fused:       # (this rank's eight totals, healthy): the loss and the metrics come from the totals' sum over ranks
+            tail = torch.zeros(9, dtype=torch.float64, device=dev)
+            if err is None:
+                tail[:8] = self._bc_totals.to(torch.float64)
+                tail[8] = 1.0
+            dist.all_reduce(tail)
+            if float(tail[8].item()) != world:
+                raise RuntimeError(f"BC step failed on {'this' if err is not None else 'another'} rank: {err!r}")
+            totals = tail[:8].to(torch.float32)
+            if metrics is not None:
+                self._fill_metrics(metrics, totals, None, 0, 0)
+                metrics.update(frame_nll=local_metrics["frame_nll"], frame_out=local_metrics["frame_out"])
+            return (totals[0] + totals[1]) / totals[6], grads, state_out
         tail = torch.tensor([0.0 if err is not None else float(loss) * m_local, 0.0 if err is not None else 1.0], device=dev)
         dist.all_reduce(tail)           # (sum over ranks of loss x local frames, number of healthy ranks)
         if float(tail[1].item()) != world:
@@ -659,10 +787,14 @@ class BCTrainer:
         return tail[0] / m_global, grads, state_out
 
     @torch.no_grad()
-    def step(self, img_u8, first, state_in, act_buttons, act_camera):
-        """One optimiser step on this rank's shard of the batch.  Returns (global mean loss, state_out)."""
+    def step(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None):
+        """One optimiser step on this rank's shard of the batch.  Returns (global mean loss, state_out).  frame_weight / metrics: as
+        loss_and_grads (the weighted loss sum w nll / sum w over all ranks; global metrics)."""
         self._need_optimizer_state()
-        loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera)
+        if frame_weight is None and metrics is None:
+            loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera)
+        else:
+            loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, frame_weight=frame_weight, metrics=metrics)
         names = [n for n in self.trainable if n in grads]
         found_inf = torch.zeros(1, dtype=torch.int32, device=img_u8.device) if self.scaled else None
         # one launch for all tensors (th.optim.Adam(policy.parameters()).step(), behavioural_cloning.py:122); in the fp16 mode it
