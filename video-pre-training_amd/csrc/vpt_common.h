@@ -13,6 +13,7 @@ typedef _Float16 op16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 op16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 op16x8 __attribute__((ext_vector_type(8)));
 #define VPT_MFMA_32X32X16 __builtin_amdgcn_mfma_f32_32x32x16_f16
+#define VPT_MFMA_16X16X32 __builtin_amdgcn_mfma_f32_16x16x32_f16
 typedef __fp16 tr16x4 __attribute__((ext_vector_type(4)));   // element type the f16 transpose-read builtin is declared with
 #define VPT_DS_READ_TR16_B64 __builtin_amdgcn_ds_read_tr16_b64_v4f16
 #define VPT_OPERAND_NAME "fp16"
@@ -22,6 +23,7 @@ typedef __bf16 op16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 op16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 op16x8 __attribute__((ext_vector_type(8)));
 #define VPT_MFMA_32X32X16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
+#define VPT_MFMA_16X16X32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
 typedef __bf16 tr16x4 __attribute__((ext_vector_type(4)));
 #define VPT_DS_READ_TR16_B64 __builtin_amdgcn_ds_read_tr16_b64_v4bf16
 #define VPT_OPERAND_NAME "bf16"

@@ -27,6 +27,8 @@
 //     covers 16 consecutive pixels of ONE image row (80-byte pixel stride -> 16 distinct bank slots),
 //   - halo ds_write_b128 are ordered so each 8-lane group hits 8 distinct 16-byte slots.
 // Two workgroups per CU (78.6 KB LDS, <= 256 VGPRs) hide each other's barriers and epilogues.
+// The FORWARD modes run the same tile on v_mfma_f32_16x16x32 (8 pixel rows x 4 cout groups of 16x16 accumulators per wave) with an epilogue in
+// the accumulators' own layout -- see M16 in the kernel; what is said above about fragments and the epilogue describes the dgrad modes.
 #include "vpt_common.h"
 #include "vpt_kernels.h"
 #include <stdlib.h>
@@ -46,6 +48,9 @@
 #define CONV_ABLATE 0
 #endif
 
+#ifndef VPT_CONV_MFMA16
+#define VPT_CONV_MFMA16 1   // 1: the forward modes run their main loop on v_mfma_f32_16x16x32 (see M16 in the kernel); 0: every mode on 32x32x16
+#endif
 #define A_RS 80
 #define A_BYTES (324 * A_RS)            // 25920
 #define B_BYTES (3 * 128 * 64)          // 24576 per buffer (unpadded, swizzled)
@@ -77,6 +82,19 @@ __device__ __forceinline__ int sub_row(int i) { return ((i >> 4) ^ (i >> 2) ^ (i
 // per-wave program, but the step's 24 KB weight tile is fetched ONCE for 512 pixels instead of once per co-resident workgroup: half
 // the weight DMA (288 KB per 256 pixels and K = 1152 before -- the largest stream on a CU's memory path) and
 // 11 % less halo (34 x 18 instead of 2 x 18 x 18 pixels).
+// M16 accumulators: the four 16x16 accumulators (cout groups u) of one pixel row live in ONE 16-register tuple, so the register allocator
+// places them like the 32x32 accumulators (whole aligned blocks, no fragmentation between 4-register tuples)
+template <int U> __device__ __forceinline__ f32x4 ac_get(const f32x16& v) {
+  return __builtin_shufflevector(v, v, 4 * U, 4 * U + 1, 4 * U + 2, 4 * U + 3);
+}
+template <int U> __device__ __forceinline__ void ac_set(f32x16& v, const f32x4 c) {
+  const f32x16 w = __builtin_shufflevector(c, c, 0, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1);
+  if constexpr (U == 0) v = __builtin_shufflevector(v, w, 16, 17, 18, 19, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+  else if constexpr (U == 1) v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 16, 17, 18, 19, 8, 9, 10, 11, 12, 13, 14, 15);
+  else if constexpr (U == 2) v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 4, 5, 6, 7, 16, 17, 18, 19, 12, 13, 14, 15);
+  else v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19);
+}
+
 template <bool TRACE, int MODE, int TR = 16>
 __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args a) {
   static_assert(TR == 16 || TR == 32, "tile rows");
@@ -112,13 +130,26 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   constexpr bool CLAMP_RELU = (MODE == 1 || MODE == 5) && !VPT_EPI_NO_CLAMP_RELU;
   constexpr float RELU_S = CLAMP_RELU ? 0x1p-40f : 1.f, RELU_INV = 0x1p40f;
   constexpr bool BWD = (MODE == 2 || MODE == 3 || MODE == 6), HAS_RES = (MODE == 1 || MODE == 3 || MODE == 5), USE_X = BWD, POOL = (MODE == 4 || MODE == 7), RES_AFF = MODE == 5;
+  // M16 (forward modes): main loop on v_mfma_f32_16x16x32.  Wave tile 8 pixel rows x 64 couts = 8 x 4 accumulators of 16 pixels x 16 couts;
+  // weights are the A operand, pixels the B operand, one ds_read_b128 per fragment carries the whole K = 32 of a tap.
+  //   - halo image: the 64-byte record of halo pixel P starts at 80 P + 16 (P & 1) -- odd pixels use the pitch's pad chunk in FRONT -- and MFMA
+  //     column c holds pixel pcol(c) of the row: the even pixels on lanes {0-3, 12-15}, the odd ones on {4-11}.  The hardware serves a
+  //     ds_read_b128 in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...: lanes that read chunk q of even (odd) pixels together
+  //     with lanes that read chunk q + 1 of odd (even) pixels.  16-byte slot mod 16 = 5 P + q + (P & 1): the even pixels of 16 consecutive
+  //     ones give the 8 even (odd) slots, the odd pixels the other 8, for every tap offset dx -- conflict-free.  (With the plain 80 P image
+  //     three of the sixteen slots of every group are hit twice.)
+  //   - weight fragment of cout group u = 2 blk + b: MFMA row r <-> cout 32 blk + 8 (r >> 2) + 4 b + (r & 3), so the two accumulators of a
+  //     32-cout block give lane (c, q) couts 8 q .. 8 q + 7: 16 contiguous bytes of its pixel's record.  Under the packed image's swizzle
+  //     ((cout >> 2) & 3) the four rows of one bank class (r & 3) read chunk positions q0 ^ s, (q0 + 1) ^ (s + 2), (q0 + 1) ^ s, q0 ^ (s + 2)
+  //     (s = b) in a hardware lane group: all four, conflict-free, the swizzle stays as it is.
+  constexpr bool M16 = VPT_CONV_MFMA16 && (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 5 || MODE == 7);
   constexpr bool DEFER_STORES = MODE != 3;   // mode 3 holds skip + xin pieces as well: no registers left for the packed results
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_SZ];
   const int tid = threadIdx.x, lane = tid & 63;
   // profiling (vpt_conv3x3_set_trace): CU id + 100 MHz timestamps of the tile's phases
   int cu_key = -1;
   long long t_trace[3];
-  if (TRACE && tid == 0) {
+  if (TRACE && (M16 || tid == 0)) {   // (M16: wave-uniform, so the stamps stay in scalar registers across the main loop)
     t_trace[0] = wall_clock64();
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID: cu_id[11:8] sh_id[12] se_id[15:13]
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_XCC_ID[3:0]
@@ -148,13 +179,15 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
 #pragma unroll
   for (int m = 0; m < NA; ++m) {
     const int q = tid + NTHR * m;
-    const int P = ((q >> 5) << 3) + (q & 7), part = (q >> 3) & 3;
+    // M16: the 8 lanes of a ds_write_b128 group carry 4 pixels of one parity x 2 parts (slots 2 k + part + const mod 8: all eight)
+    const int P = M16 ? ((q >> 5) << 3) + 2 * (q & 3) + ((q >> 4) & 1) : ((q >> 5) << 3) + (q & 7);
+    const int part = M16 ? 2 * ((q >> 3) & 1) + ((q >> 2) & 1) : (q >> 3) & 3;
     a_loff[m] = -1;
     a_gbyte[m] = 0u;
     if (P < HPIX) {
       const int hy = P / 18, hx = P - hy * 18;
       const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-      a_loff[m] = P * A_RS + part * 16;
+      a_loff[m] = P * A_RS + part * 16 + (M16 ? 16 * (P & 1) : 0);
       if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
         a_gbyte[m] = (unsigned)((y * a.W + x) * 32 + part * 8) * 2u;
         a_inside |= 1u << m;
@@ -162,6 +195,13 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     }
   }
   const op16_t* xplane = a.x + (size_t)f * NCB * HW * 32;
+  // M16: chunk m of a thread lies NTHR / 4 halo pixels behind chunk m - 1 (same parity, same part): ONE address register and constant
+  // offsets; only the last chunk can fall beyond the halo
+  constexpr int H16_STR = (NTHR / 4) * A_RS;
+  static_assert(((NA - 2) * NTHR + NTHR - 1) / 32 * 8 + 7 < HPIX, "all chunks but a thread's last are inside the halo");
+  const int a_l0 = a_loff[0];
+  const bool a_lastok = a_loff[NA - 1] >= 0;
+#define HALO_WR16(m_) do { if ((m_) < NA - 1 || a_lastok) *(u32x4*)(smem + a_l0 + (m_) * H16_STR) = ((a_inside >> (m_)) & 1u) ? areg[m_] : zero4; } while (0)
   // weight DMA: wave w moves pieces (NWAVE*m + w), m = 0..NDMA-1, of the 24 KB step tile; lane = 16-byte chunk
   const op16_t* wbase = a.wpk + (size_t)nt * NCB * 9 * 4096 + (size_t)(w * 64 + lane) * 8;
   unsigned char* bdst = smem + A_SZ + w * 1024;
@@ -195,6 +235,10 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     c0f = a.coef[2 * f];
     c1f = a.coef[2 * f + 1];
   }
+  if constexpr (M16) {   // wave-uniform, but computed by vector instructions: held in a scalar register across the main loop
+    rstd = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rstd)));
+    mean = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mean)));
+  }
   float rgate = 1.f;
   if (GATE) {      // everything the epilogue adds is linear in the scale: fold rstd0 into the coefficients
     float mg;
@@ -226,10 +270,16 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
 #define WRITE_HALO()                                                                                      \
   _Pragma("unroll") for (int m_ = 0; m_ < NA; ++m_)                                                       \
     if (a_loff[m_] >= 0) *(u32x4*)(smem + a_loff[m_]) = ((a_inside >> m_) & 1u) ? areg[m_] : zero4
-  WRITE_HALO();
+  if constexpr (M16) {
+#pragma unroll
+    for (int m = 0; m < NA; ++m) HALO_WR16(m);
+  } else {
+    WRITE_HALO();
+  }
   __syncthreads();
 
   f32x16 acc[4][2];
+  f32x16 ac[8];              // M16: [pixel row j of the wave's 8], elements 4 u .. 4 u + 3 = cout group u (ac_get / ac_set)
   f32x16 zero16;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
@@ -239,6 +289,19 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   const int bsw = (l31 >> 2) & 3;
   const unsigned char* bL0 = smem + A_SZ + (wn * 64 + l31) * 64 + (((0 + hi) ^ bsw) << 4);  // ks = 0
   const unsigned char* bL1 = smem + A_SZ + (wn * 64 + l31) * 64 + (((2 + hi) ^ bsw) << 4);  // ks = 1
+
+  // M16 fragment bases: lane = (MFMA column / row c16, K chunk q16)
+  const int c16 = lane & 15, q16 = lane >> 4;
+  const int pcol = (c16 < 4) ? 2 * c16 : ((c16 < 12) ? 2 * (c16 - 4) + 1 : 2 * (c16 - 8));   // pixel column of MFMA column c16
+  // (LDS pointers the compiler cannot see behind: every fragment read is base + a 16-bit immediate; folded into the array's address the larger
+  // offsets no longer fit the instruction and each costs an address register)
+  typedef const __attribute__((address_space(3))) unsigned char* lds_cptr;
+  lds_cptr aLe = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (pcol & 1);        // taps dx = 0, 2: halo pixel parity = pcol's
+  lds_cptr aLo = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (1 - (pcol & 1));  // tap dx = 1
+  // cout group u = 2 blk + b: row 32 blk + 8 (c16 >> 2) + 4 b + (c16 & 3), swizzle ((row >> 2) & 3) = (2 (c16 >> 2) + b) & 3
+  lds_cptr bW0 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2)) & 3)) << 4);
+  lds_cptr bW1 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + 4 + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2) + 1) & 3)) << 4);
+  if constexpr (M16) { asm volatile("" : "+v"(aLe), "+v"(aLo), "+v"(bW0), "+v"(bW1)); }
 
   // epilogue addressing (needed early: the residual is requested during the last channel block)
   // Operands are SWAPPED in the MFMA (weights = A rows, pixels = B columns): a lane holds ONE pixel (column l31 of the
@@ -292,6 +355,13 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
     _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_) rq[m_][n2_][p_] = EPI_LD(a.res, m_, n2_, p_)
 #endif
+  // M16: lane (c16, q16) owns bytes 16 q16 .. + 15 of pixel pcol(c16)'s 64-byte record in every (pixel row j, 32-cout block n2): residual, xin and
+  // output move as ONE 16-byte access per lane, 1024 contiguous bytes per instruction, in the accumulators' own layout.
+  const unsigned voff16 = (unsigned)(((ty0 + wm * 8) * a.W + tx0 + pcol) * 32 + 8 * q16) * 2u;
+  const unsigned gj_b = (unsigned)a.W * 64u;           // + j * gj_b: one image row further down (bytes)
+  u32x4 rq16[8][2];                                    // residual [pixel row j][n2]
+#define EPI_LD16(ptr_, j_, n2_) (*(const u32x4*)((const char*)((ptr_) + cbase[n2_]) + (voff16 + (unsigned)(j_) * gj_b)))
+#define XR16(j_) do { rq16[j_][0] = EPI_LD16(resp, j_, 0); rq16[j_][1] = EPI_LD16(resp, j_, 1); } while (0)
 
   // ---- main loop ----------------------------------------------------------------------------------------------------
   // One K step = one kernel row (3 taps) of one 32-channel block = 6 groups (tap dx, 16-channel half ks) of 8 MFMAs per
@@ -422,8 +492,125 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     }                                                                                                     \
   } while (0)
 
-  if (TRACE && tid == 0) t_trace[1] = wall_clock64();
-  if (CONV_ABLATE != 2) {
+  // ---- M16 main loop: one K step = 3 taps x 4 cout groups x 8 pixel rows = 96 MFMAs of 16x16x32 per wave, in 12 groups of 8 (one cout
+  // group over the 8 pixel rows).  Registers: the 8 pixel fragments of the CURRENT tap (32) + a double-buffered weight fragment (8) = 40.
+  // A group requests the weight fragment of the next group behind its first MFMA; the tap's last group also refills each pixel fragment for
+  // the next tap right behind the MFMA that used it last.  Vector-memory operations keep the order and count of the 32x32 loop (weight DMA,
+  // then halo / residual), one slot per group; the step's barrier sits in front of its LAST group, which holds every fragment it needs and
+  // requests the next step's first ones behind the barrier.
+  op16x8 fp[8], fw[2];
+#define PA(j_, dy_, dx_) fp[j_] = *(const __attribute__((address_space(3))) op16x8*)((((dx_) & 1) ? aLo : aLe) + (((j_) + (dy_)) * 18 + (dx_)) * A_RS)
+#define WB(tap_, u_, boff_) fw[(u_) & 1] = *(const __attribute__((address_space(3))) op16x8*)((((u_) & 1) ? bW1 : bW0) + (boff_) + (tap_) * (128 * 64) + ((u_) >> 1) * (32 * 64))
+#define M16A(j_, u_) ac_set<(u_)>(ac[j_], VPT_MFMA_16X16X32(fw[(u_) & 1], fp[j_], ac_get<(u_)>(ac[j_]), 0, 0, 0))
+  // cout group u_ < 3 of a tap: WLD = the next group's weight fragment, X = the group's vector-memory slot
+#define G16(MM_, u_, WLD, X)                                                                              \
+  do {                                                                                                    \
+    MM_(0, u_); WLD; SB();                                                                                \
+    MM_(1, u_); SB();                                                                                     \
+    MM_(2, u_); SB();                                                                                     \
+    MM_(3, u_); X; SB();                                                                                  \
+    MM_(4, u_); SB();                                                                                     \
+    MM_(5, u_); SB();                                                                                     \
+    MM_(6, u_); SB();                                                                                     \
+    MM_(7, u_); SB();                                                                                     \
+  } while (0)
+  // cout group 3: every pixel fragment is refilled for tap (ndy_, ndx_) behind its last use
+#define G16R(MM_, WLD, X, ndy_, ndx_)                                                                     \
+  do {                                                                                                    \
+    MM_(0, 3); SB(); WLD; PA(0, ndy_, ndx_); SB();                                                              \
+    MM_(1, 3); SB(); PA(1, ndy_, ndx_); SB();                                                                   \
+    MM_(2, 3); SB(); PA(2, ndy_, ndx_); SB();                                                                   \
+    MM_(3, 3); SB(); PA(3, ndy_, ndx_); X; SB();                                                                \
+    MM_(4, 3); SB(); PA(4, ndy_, ndx_); SB();                                                                   \
+    MM_(5, 3); SB(); PA(5, ndy_, ndx_); SB();                                                                   \
+    MM_(6, 3); SB(); PA(6, ndy_, ndx_); SB();                                                                   \
+    MM_(7, 3); SB(); PA(7, ndy_, ndx_); SB();                                                                   \
+  } while (0)
+#define TAP16(MM_, dy_, dx_, X0, X1, X2, X3)                                                              \
+  do {                                                                                                    \
+    G16(MM_, 0, WB(dx_, 1, boff_), X0);                                                                   \
+    G16(MM_, 1, WB(dx_, 2, boff_), X1);                                                                   \
+    G16(MM_, 2, WB(dx_, 3, boff_), X2);                                                                   \
+    G16R(MM_, WB((dx_) + 1, 0, boff_), X3, dy_, (dx_) + 1);                                               \
+  } while (0)
+#define CONV_STEP16(cb_, dy_, NEXT_DY, PRE_A, WR_A, PRE_R, LAST)                                          \
+  do {                                                                                                    \
+    const int s_ = (cb_) * 3 + (dy_);                                                                     \
+    const int boff_ = (s_ & 1) * B_BYTES, noff_ = B_BYTES - boff_;                                        \
+    const op16_t* wp_ = wbase + (size_t)(s_ + 1) * 12288;                                                 \
+    unsigned char* bd_ = bdst + noff_;                                                                    \
+    const unsigned cbo_ = (unsigned)((cb_) + 1) * (unsigned)HW * 64u; /* bytes; uniform */                \
+    if (LAST) {                                                                                           \
+      TAP16(M16A, dy_, 0, NOP_(), NOP_(), NOP_(), NOP_());                                                \
+    } else {                                                                                              \
+      TAP16(M16A, dy_, 0, GLDS(0), GLDS(1), GLDS(2), GLDS(3));                                            \
+    }                                                                                                     \
+    if (PRE_A) {                                                                                          \
+      TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), do { XA(0); XA(1); } while (0), XA(2));                       \
+      G16(M16A, 0, WB(2, 1, boff_), do { XA(3); XA(4); } while (0));                                      \
+      G16(M16A, 1, WB(2, 2, boff_), XA(5));                                                               \
+      G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
+      if (VPT_CONV_HALO_ABLATE == 2) WAIT_BARRIER(0); else if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5); \
+    } else if ((PRE_R) && HAS_RES) {                                                                      \
+      TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), XR16(0), NOP_());                                             \
+      G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
+      G16(M16A, 1, WB(2, 2, boff_), NOP_());                                                              \
+      G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
+      WAIT_BARRIER(2);   /* row 0 x 2 blocks */                                                                                      \
+    } else {                                                                                              \
+      if (LAST) TAP16(M16A, dy_, 1, NOP_(), NOP_(), NOP_(), NOP_());                                      \
+      else TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), NOP_(), NOP_());                                         \
+      G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
+      G16(M16A, 1, WB(2, 2, boff_), NOP_());                                                              \
+      G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
+      if ((LAST) && !TRACE && HAS_RES && VPT_RES_LATE && VPT_RES_PREFETCH && !(VPT_EPI_ABLATE & 4)) WAIT_BARRIER(2); \
+      else WAIT_BARRIER(0);                                                                               \
+    }                                                                                                     \
+    if (WR_A) {   /* the halo of the next channel block replaces the current one: second barrier before its first read */ \
+      _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) {                                                  \
+        HALO_WR16(m_); SB();                                                                              \
+        if (m_ + 4 < NA) HALO_WR16(m_ + 4 < NA ? m_ + 4 : 0);                                             \
+        SB(); if (m_ == 0) M16A(0, 3); else if (m_ == 1) M16A(1, 3); else if (m_ == 2) M16A(2, 3); else M16A(3, 3); SB();                                                                        \
+      }                                                                                                   \
+      WAIT_BARRIER(0);                                                                                    \
+      WB(0, 0, noff_); PA(0, 0, 0); PA(1, 0, 0); PA(2, 0, 0); PA(3, 0, 0); SB();                          \
+      M16A(4, 3); SB(); PA(4, 0, 0); SB();                                                                      \
+      M16A(5, 3); SB(); PA(5, 0, 0); SB();                                                                      \
+      M16A(6, 3); SB(); PA(6, 0, 0); SB();                                                                      \
+      M16A(7, 3); SB(); PA(7, 0, 0); SB();                                                                      \
+    } else if (LAST) {                                                                                    \
+      M16A(0, 3); M16A(1, 3); M16A(2, 3); M16A(3, 3); M16A(4, 3); M16A(5, 3); M16A(6, 3); M16A(7, 3);                                    \
+    } else {                                                                                              \
+      G16R(M16A, WB(0, 0, noff_), NOP_(), NEXT_DY, 0);                                                    \
+    }                                                                                                     \
+  } while (0)
+
+  if (TRACE && (M16 || tid == 0)) t_trace[1] = wall_clock64();
+  if constexpr (M16) {
+    if (CONV_ABLATE != 2) {
+      WB(0, 0, 0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) PA(j, 0, 0);
+      SB();
+      // The accumulators start from zero: a peeled first channel block whose first tap takes C = 0 (as the 32x32 loop does) cost 27 spilled registers.
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ac[j] = zero16;
+#pragma unroll 1
+      for (int cb = 0; cb + 1 < NCB; ++cb) {
+        CONV_STEP16(cb, 0, 1, true, false, false, false);
+        CONV_STEP16(cb, 1, 2, false, false, false, false);
+        CONV_STEP16(cb, 2, 0, false, true, false, false);
+      }
+      // (the tracing instantiations hold the phase stamps as well: no residual request inside their main loop)
+      CONV_STEP16(NCB - 1, 0, 1, false, false, !TRACE && !VPT_RES_LATE && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false);
+      CONV_STEP16(NCB - 1, 1, 2, false, false, !TRACE && VPT_RES_LATE != 0 && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false);
+      CONV_STEP16(NCB - 1, 2, 0, false, false, false, true);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ac[j] = zero16;
+      __syncthreads();
+    }
+  } else if (CONV_ABLATE != 2) {
     FB_LD(0, 0, 0, 0); FA_LD(0, 0, 0, 0); FB_LD(0, 0, 1, 0); FA_LD(0, 0, 0, 1); FA_LD(0, 0, 0, 2); FA_LD(0, 0, 0, 3);
     SB();
     if (NCB > 1) {   // first channel block peeled: its first eight MFMAs take C = 0 instead of 128 zeroed registers
@@ -460,6 +647,14 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     __syncthreads();
   }
 #undef CONV_STEP
+#undef HALO_WR16
+#undef CONV_STEP16
+#undef TAP16
+#undef G16
+#undef G16R
+#undef M16A
+#undef PA
+#undef WB
 #undef WAIT_BARRIER
 #undef GROUP
 #undef GROUP_TAIL
@@ -474,19 +669,30 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
 #undef FB_LD
 
   // ---------------- epilogue ----------------
-  if (TRACE && tid == 0) t_trace[2] = wall_clock64();
+  if (TRACE && (M16 || tid == 0)) t_trace[2] = wall_clock64();
   if (CONV_ABLATE == 1) {  // profiling: keep the accumulators live, skip the epilogue
     float t = 0.f;
+    if constexpr (M16) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t += ac[j][r];
+    } else {
 #pragma unroll
     for (int m = 0; m < 4; ++m)
 #pragma unroll
       for (int n = 0; n < 2; ++n)
 #pragma unroll
         for (int r = 0; r < 16; ++r) t += acc[m][n][r];
+    }
     if (t == 12345.678f) a.y[0] = (vpt_op16)t;
     return;
   }
-  if (HAS_RES && (CONV_ABLATE == 2 || !VPT_RES_PREFETCH)) { LOAD_RES(0); LOAD_RES(1); }
+  if constexpr (M16) {
+    if (HAS_RES && (TRACE || CONV_ABLATE == 2 || !VPT_RES_PREFETCH || (VPT_EPI_ABLATE & 4))) XR16(0);
+  } else {
+    if (HAS_RES && (CONV_ABLATE == 2 || !VPT_RES_PREFETCH)) { LOAD_RES(0); LOAD_RES(1); }
+  }
   SB();
 
   f32x2 s_sum2 = {0.f, 0.f}, s_sq2 = {0.f, 0.f};   // packed fp32 (v_pk_add_f32 / v_pk_fma_f32): two values per VALU issue
@@ -687,12 +893,119 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         if (!(VPT_EPI_ABLATE & 1) || s_sum2.x == 12345.678f) *(u32x4*)((char*)(a.y + cbase[n2]) + (svoff[p] + (unsigned)m * gm_b)) = outv[m][n2][p];
     }
   };
+  // ---- M16 epilogue: everything in the accumulators' own layout.  Lane (c16, q16) holds, per pixel row j and 32-cout block n2, the 8 values of couts
+  // 8 q16 .. + 7 of pixel pcol (accumulator elements 8 n2 .. 8 n2 + 7 of ac[j]): two f32x4 of the constant table, ONE 16-byte residual load and
+  // ONE 16-byte store per lane -- whole 128-byte lines, no lane exchange anywhere.  Per value the arithmetic (fold, clamp / packed ReLU, residual
+  // FMA, rounding, v_dot2 statistics) is that of the 32x32 epilogue above.  The edge class of a row differs from "interior" only on the wave's
+  // first row (image top) and last row (image bottom).
+  // (derived from a copy of the lane id the compiler cannot see through: computed HERE, not held in registers across the main loop)
+  int lane_l = lane;
+  asm volatile("" : "+v"(lane_l));
+  const int c16_l = lane_l & 15, q16_l = lane_l >> 4;
+  const int pcol_l = (c16_l < 4) ? 2 * c16_l : ((c16_l < 12) ? 2 * (c16_l - 4) + 1 : 2 * (c16_l - 8));
+  const unsigned voff16_l = (unsigned)(((ty0 + wm * 8) * a.W + tx0 + pcol_l) * 32 + 8 * q16_l) * 2u;
+#define XR16L(j_) do { rq16[j_][0] = *(const u32x4*)((const char*)(resp + cbase[0]) + (voff16_l + (unsigned)(j_) * gj_b)); rq16[j_][1] = *(const u32x4*)((const char*)(resp + cbase[1]) + (voff16_l + (unsigned)(j_) * gj_b)); } while (0)
+  const int x16_ = tx0 + pcol_l;
+  const int ex16 = (x16_ == 0) ? 0 : ((x16_ == a.W - 1) ? 2 : 1);
+  const int eo_top = (ty0 + wm * 8 == 0) ? 0 : 3 * 128, eo_bot = (ty0 + wm * 8 + 7 == a.H - 1) ? 6 * 128 : 3 * 128;
+  const float* kk16 = (const float*)(smem + KK_O) + ex16 * 128 + wn * 64 + 8 * q16_l;
+#define EO16(j_) ((j_) == 0 ? eo_top : ((j_) == 7 ? eo_bot : 3 * 128))
+  auto epilogue16 = [&](auto nv_) __attribute__((always_inline)) {
+    constexpr int NV = decltype(nv_)::value;
+    u32x4 outv[8][2];          // packed results: all stores are issued after the last load has been consumed (see the 32x32 epilogue)
+    f32x4 kq[2][2];            // constant table [parity of chunk c = 2 j + n2][half h], one chunk ahead
+#define LOAD_KK16(c_)                                                                                     \
+  do {                                                                                                    \
+    const float* kp_ = kk16 + EO16((c_) >> 1) + ((c_) & 1) * 32;                                          \
+    kq[(c_) & 1][0] = *(const f32x4*)kp_; kq[(c_) & 1][1] = *(const f32x4*)(kp_ + 4);                     \
+  } while (0)
+    LOAD_KK16(0);
+    SB();
+    const f32x2 zero2 = {0.f, 0.f};
+    const f32x2 rstd2 = {rstd * RELU_S, rstd * RELU_S}, ress2 = {res_s, res_s};
+    const f32x2 relu_inv2 = {RELU_INV, RELU_INV};
+    const float* btab = (const float*)(smem + BT_O) + wn * 64 + 8 * q16_l;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (HAS_RES && j == 0) XR16L(1);
+      if (HAS_RES && j < 6) XR16L(j + 2);   // rolling prefetch, two rows ahead (row 0 was requested during the last channel block)
+      SB();
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2) {
+        if (2 * j + n2 < 15) { LOAD_KK16(2 * j + n2 + 1); SB(); }
+        if (n2 >= NV) continue;
+        f32x4 bq[2];
+        if (RES_AFF) {
+          bq[0] = *(const f32x4*)(btab + n2 * 32); bq[1] = *(const f32x4*)(btab + n2 * 32 + 4);
+          SB();
+        }
+        u32x2 pk[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          f32x2 v01 = {ac[j][8 * n2 + 4 * h + 0], ac[j][8 * n2 + 4 * h + 1]}, v23 = {ac[j][8 * n2 + 4 * h + 2], ac[j][8 * n2 + 4 * h + 3]};
+          const f32x4 k4 = kq[n2][h];
+          const f32x2 k01 = {k4.x, k4.y}, k23 = {k4.z, k4.w};
+          if (PACKED_RELU) {
+            v01 = rstd2 * v01 + k01;
+            v23 = rstd2 * v23 + k23;
+          } else if (CLAMP_RELU) {
+            v01 = pk_fma_clamp01(rstd2, v01, k01);
+            v23 = pk_fma_clamp01(rstd2, v23, k23);
+          } else {
+            v01 = __builtin_elementwise_max(rstd2 * v01 + k01, zero2);
+            v23 = __builtin_elementwise_max(rstd2 * v23 + k23, zero2);
+          }
+          if (HAS_RES) {
+            const uint32_t ra = h ? rq16[j][n2].z : rq16[j][n2].x, rb = h ? rq16[j][n2].w : rq16[j][n2].y;
+            const f32x2 r01 = {op16_lo_to_f32(ra), op16_hi_to_f32(ra)}, r23 = {op16_lo_to_f32(rb), op16_hi_to_f32(rb)};
+            if (RES_AFF) {
+              const f32x4 b4 = bq[h];
+              const f32x2 b01 = {b4.x, b4.y}, b23 = {b4.z, b4.w};
+              if (CLAMP_RELU) {
+                v01 = ress2 * r01 + __builtin_elementwise_fma(v01, relu_inv2, b01);
+                v23 = ress2 * r23 + __builtin_elementwise_fma(v23, relu_inv2, b23);
+              } else {
+                v01 = ress2 * r01 + (v01 + b01);
+                v23 = ress2 * r23 + (v23 + b23);
+              }
+            } else if (CLAMP_RELU) {
+              v01 = __builtin_elementwise_fma(v01, relu_inv2, r01);
+              v23 = __builtin_elementwise_fma(v23, relu_inv2, r23);
+            } else {
+              v01 += r01;
+              v23 += r23;
+            }
+          }
+          pk[h].x = pack_op16x2(v01.x, v01.y);
+          pk[h].y = pack_op16x2(v23.x, v23.y);
+          if (PACKED_RELU) {   // ReLU on the rounded bit patterns (bit-identical to an fp32 maximum before the rounding, see the 32x32 epilogue)
+            pk[h].x = relu_op16x2(pk[h].x);
+            pk[h].y = relu_op16x2(pk[h].y);
+          }
+          s_sum2.x = dot2_op16(pk[h].x, OP16_ONE2, s_sum2.x);   // frame statistics of the STORED tensor
+          s_sum2.y = dot2_op16(pk[h].y, OP16_ONE2, s_sum2.y);
+          s_sq2.x = dot2_op16(pk[h].x, pk[h].x, s_sq2.x);
+          s_sq2.y = dot2_op16(pk[h].y, pk[h].y, s_sq2.y);
+        }
+        outv[j][n2] = u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
+      }
+    }
+#undef LOAD_KK16
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int n2 = 0; n2 < NV; ++n2)
+        if (!(VPT_EPI_ABLATE & 1) || s_sum2.x == 12345.678f) *(u32x4*)((char*)(a.y + cbase[n2]) + (voff16_l + (unsigned)j * gj_b)) = outv[j][n2];
+  };
   if constexpr (POOL) {
     // The four pointers only this epilogue uses are read from the kernarg segment HERE, through a pointer the compiler cannot see behind: taken from
     // `a` they are loaded with the rest of the arguments at kernel entry and sit in eight scalar registers through the whole main loop -- in the
     // arg-max mode (7) that was the eight registers too many (8 SGPRs spilled to VGPR lanes around the loop).
     const __attribute__((address_space(4))) VptConv3x3Args* late = (const __attribute__((address_space(4))) VptConv3x3Args*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(late));
+    int tid_p = threadIdx.x;   // M16: the thread-indexed addressing of phase 2 is derived HERE, not held across the main loop
+    if constexpr (M16) { asm volatile("" : "+v"(tid_p)); }
+    const int tid = tid_p, lane = tid_p & 63;
     vpt_op16* const seam_r_p = late->seam_r;
     vpt_op16* const seam_c_p = late->seam_c;
     vpt_op16* const pool_mask_p = late->pool_mask;
@@ -701,7 +1014,36 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     // 16 extra bytes spread a column of pixels over the banks).  The tile reuses the halo / weight buffers: every wave must be past
     // its last fragment read first.  A lane holds 4 consecutive channels of one pixel per accumulator group: one ds_write_b64 each.
     __syncthreads();
-    {
+    if constexpr (M16) {   // one ds_write_b128 per lane and (pixel row, 32-cout block): couts 8 q16 .. + 7 of pixel (wm 8 + j, pcol)
+      const f32x2 zero2 = {0.f, 0.f};
+      const f32x2 rstd2 = {rstd, rstd};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float* ke = kk16 + EO16(j);
+        unsigned char* dst = smem + ((wm * 8 + j) * 16 + pcol_l) * PT_RS + (wn * 64 + 8 * q16_l) * 2;
+#pragma unroll
+        for (int n2 = 0; n2 < 2; ++n2) {
+          if (!nvalid[n2]) continue;
+          u32x2 pk[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const f32x4 k4 = *(const f32x4*)(ke + n2 * 32 + 4 * h);
+            const f32x2 k01 = {k4.x, k4.y}, k23 = {k4.z, k4.w};
+            f32x2 v01 = {ac[j][8 * n2 + 4 * h + 0], ac[j][8 * n2 + 4 * h + 1]}, v23 = {ac[j][8 * n2 + 4 * h + 2], ac[j][8 * n2 + 4 * h + 3]};
+            if (PMASK) {
+              v01 = __builtin_elementwise_max(rstd2 * v01 + k01, zero2);
+              v23 = __builtin_elementwise_max(rstd2 * v23 + k23, zero2);
+            } else {
+              v01 = rstd2 * v01 + k01;
+              v23 = rstd2 * v23 + k23;
+            }
+            pk[h].x = pack_op16x2(v01.x, v01.y);
+            pk[h].y = pack_op16x2(v23.x, v23.y);
+          }
+          *(u32x4*)(dst + n2 * 64) = u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
+        }
+      }
+    } else {
       const float* kk = (const float*)(smem + KK_O);
       const f32x2 zero2 = {0.f, 0.f};
       const f32x2 rstd2 = {rstd, rstd};
@@ -855,10 +1197,17 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         if (ch < a.Cout) atomicAdd(chs_out_p + ((size_t)f * a.Cout + ch) * 2 + (k >> 3), (double)t);
       }
     }
+  } else if constexpr (M16) {
+    if (nvalid[1]) epilogue16(std::integral_constant<int, 2>{});
+    else if (nvalid[0]) epilogue16(std::integral_constant<int, 1>{});
   } else {
   if (nvalid[1]) epilogue(std::integral_constant<int, 2>{});
   else if (nvalid[0]) epilogue(std::integral_constant<int, 1>{});
   }
+#undef EO16
+#undef XR16L
+#undef XR16
+#undef EPI_LD16
   float s_sum = s_sum2.x + s_sum2.y, s_sq = s_sq2.x + s_sq2.y;
   if (GATE) {      // one fp64 atomic per tile: this tile's share of sum rstd0 dy xin
     float* red = (float*)(smem + KK_O + KK_BYTES);
