@@ -404,7 +404,8 @@ int vpt_masked_attention_backward_episodes(const float* qkvr, const float* kmem,
  * stats_in are the statistics of the layer's INPUT (Cin*H*W elements).  With dy = NULL the layer is followed by the
  * max-pool and (dpooled, argmax) are given instead: the pool's backward is applied on the fly.  scratch: fp32 work buffer of
  * vpt_workspace_bytes(VPT_WS_CONV_BACKWARD_PREPARE, frames, 0, 0, 0, Cout) bytes (per-frame sums, then per-32-frame partial sums of d_sa / d_sg that
- * are added in a fixed order).  W must be 8, 16, 32 or 64. */
+ * are added in a fixed order).  W in {8, 16, 32, 64} runs the tuned kernel; with dy given any other W >= 2 is served by a slower
+ * pixel-per-thread kernel (the (dpooled, argmax) entry keeps the restriction). */
 int vpt_conv_backward_prepare(const void* dy, const void* dpooled, const uint8_t* argmax, const void* y, const void* res,
                               const double* stats_in, const float* edge_sa, const float* edge_sg, void* dacc, double* t12,
                               float* coef, float* d_sa, float* d_sg, float* scratch, int frames, int H, int W, int Cin, int Cout, void* stream);

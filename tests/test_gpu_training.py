@@ -365,17 +365,19 @@ def test_block_backward_gated_dgrad_equals_the_two_step_path(frames, h, c, fmt):
     assert e["t12"] < 4 * tol and e["coef"] < 4 * tol and e["dsa"] < 4 * tol and e["dsg"] < 4 * tol, e
 
 
+@pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 @pytest.mark.parametrize("frames,h,cin,cout", [(3, 16, 64, 96), (2, 32, 32, 128), (1, 64, 64, 32)])
-def test_conv_wgrad_kernel(frames, h, cin, cout):
+def test_conv_wgrad_kernel(frames, h, cin, cout, fmt):
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16}[fmt]      # the kernel is built per operand format
     g = torch.Generator().manual_seed(14)
-    dacc = torch.randn(frames, cout, h, h, generator=g).to(torch.bfloat16).float()
-    x = torch.randn(frames, cin, h, h, generator=g).to(torch.bfloat16).float()
+    dacc = torch.randn(frames, cout, h, h, generator=g).to(dt).float()
+    x = torch.randn(frames, cin, h, h, generator=g).to(dt).float()
     xp = torch.nn.functional.pad(x, (1, 1, 1, 1))
     ref = torch.zeros(cout, 9, cin)
     for kh in range(3):
         for kw in range(3):
             ref[:, kh * 3 + kw, :] = torch.einsum("foyx,fcyx->oc", dacc, xp[:, :, kh:kh + h, kw:kw + h])
-    out = ops.conv3x3_wgrad(packing.nchw_to_blocked(dacc).to(DEV), packing.nchw_to_blocked(x).to(DEV))
+    out = ops.conv3x3_wgrad(packing.nchw_to_blocked(dacc, dtype=dt).to(DEV), packing.nchw_to_blocked(x, dtype=dt).to(DEV))
     torch.cuda.synchronize()
     err = _l2(out.cpu(), ref)
     assert err < 2e-3, f"wgrad rel L2 {err}"

@@ -500,6 +500,71 @@ __global__ __launch_bounds__(256) void vpt_conv_bwd_prep_kernel(VptConvBwdPrepAr
 }
 
 // ------------------------------------------------------------------------------------------------
+// vpt_conv_bwd_prep_anyw: the same preparation (dy given, with or without res) for the image widths the column-per-thread mapping above does
+// not cover -- W not a power of two, or above 64.  The network has none, but the forward and dgrad kernels take any width, and a layer has to
+// be differentiable at every shape it can run at (tests/test_gpu_cnn_backward_fp64.py: 16 x 80).  Thread = (channel octet, pixel slot): pixel
+// p = slot + 64 i of the plane; the edge class is a per-pixel value here, so the nine class sums live in 72 registers and take dz by
+// compare-and-add -- about twice the vector work per element of the kernel above, not tuned.  Per element the arithmetic is the same
+// (dz * rstd, fmaf(dz, v, tv)); the sums are reduced in a fixed order (butterfly over the 16 lanes of an octet -> one LDS row per wave -> the
+// four waves in order) and land in the same sbuf layout, so vpt_conv_bwd_finish_kernel and vpt_conv_bwd_sum_kernel follow unchanged.
+template <bool HAS_RES>
+__global__ __launch_bounds__(256) void vpt_conv_bwd_prep_anyw_kernel(VptConvBwdPrepArgs a) {
+  __shared__ float stage_[EDGE_STAGE_FLOATS];
+  __shared__ float red_[4];
+  const int HW = a.H * a.W;
+  const int cb = blockIdx.x % a.CB, f = blockIdx.x / a.CB;
+  float mean, rstd;
+  frame_mean_rstd(a.stats_in, f, a.inv_count_in, mean, rstd);
+  const int oct = threadIdx.x & 3, slot = threadIdx.x >> 2;
+  const size_t plane = ((size_t)(f * a.CB + cb) * HW) * 32 + oct * 8;
+  float s[9][8];
+#pragma unroll
+  for (int c = 0; c < 9; ++c)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s[c][k] = 0.f;
+  float tv = 0.f;
+  for (int p = slot; p < HW; p += 64) {
+    const int y = p / a.W, x = p - y * a.W;
+    const int e = ((y == 0) ? 0 : ((y == a.H - 1) ? 2 : 1)) * 3 + ((x == 0) ? 0 : ((x == a.W - 1) ? 2 : 1));
+    const size_t off = plane + (size_t)p * 32;
+    float v[8], dy[8], o[8];
+    unpack8(VPT_LD_STREAM((const u32x4*)(a.y + off)), v);
+    unpack8(VPT_LD_STREAM((const u32x4*)(a.dy + off)), dy);
+    if (HAS_RES) {
+      float rr[8];
+      unpack8(VPT_LD_STREAM((const u32x4*)(a.res + off)), rr);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] -= rr[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float dz = (v[k] > 0.f) ? dy[k] : 0.f;
+      o[k] = dz * rstd;
+      tv = fmaf(dz, v[k], tv);
+#pragma unroll
+      for (int c = 0; c < 9; ++c) s[c][k] += (e == c) ? dz : 0.f;
+    }
+    VPT_ST_STREAM(pack8(o), (u32x4*)(a.dacc + off));
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;      // (lane & 3 == oct: lanes 0..3 hold one octet each after the butterfly)
+#pragma unroll
+  for (int c = 0; c < 9; ++c)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float r = sum_oct16(s[c][k]);
+      if (lane < 4) stage_[wave * (9 * 32) + c * 32 + oct * 8 + k] = r;
+    }
+  tv = wave_sum(tv);
+  if (lane == 0) red_[wave] = tv;
+  __syncthreads();
+  const int Cout = a.CB * 32;
+  float* srow = a.sbuf + (size_t)f * (9 * Cout + a.CB);
+  if (threadIdx.x == 0) srow[9 * Cout + cb] = (red_[0] + red_[1]) + (red_[2] + red_[3]);
+  for (int i = threadIdx.x; i < 9 * 32; i += 256)
+    srow[(i >> 5) * Cout + cb * 32 + (i & 31)] = (stage_[i] + stage_[288 + i]) + (stage_[576 + i] + stage_[864 + i]);
+}
+
+// ------------------------------------------------------------------------------------------------
 // vpt_conv_bwd_prep_pooled (round 5): the same preparation for the layer in front of the max-pool when its forward was the pool-fused
 // convolution with arg-max masks (vpt_conv3x3_kernel mode 7) -- no pre-pool tensor, no arg-max bytes.  Inputs at POOLED resolution:
 // dpooled, the pooled tensor P (the ReLU gate is [P > 0] and the layer's value at the arg-max is P itself) and the 9-bit masks.
@@ -776,11 +841,19 @@ extern "C" int vpt_conv_bwd_prep_launch(const VptConvBwdPrepArgs* a0, hipStream_
     hipLaunchKernelGGL(vpt_conv_bwd_sum_kernel, dim3((2 * 9 * a.CB * 32 + 255) / 256), dim3(256), 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
   }
-  if (a.W < 8 || a.W > 64 || (a.W & (a.W - 1))) return -1;  // column-per-thread mapping: W in {8,16,32,64}
-  if (!a.dy && (!a.dpooled || !a.argmax || (a.H & 1) || (a.W & 1))) return -1;
-  a.wshift = 31 - __builtin_clz((unsigned)a.W);
   const long grid = (long)a.frames * a.CB;
   if (grid > 0x7fffffffL) return -2;
+  const int fin_blocks = (a.frames + 3) / 4 + ((9 * a.CB * 32 + 255) / 256) * ((a.frames + FIN_FB - 1) / FIN_FB);
+  if (a.W < 8 || a.W > 64 || (a.W & (a.W - 1))) {   // not the column-per-thread mapping's W in {8,16,32,64}: the pixel-per-thread kernel, for the dy entry
+    if (!a.dy || a.gate_u || !a.y || !a.dacc || a.H < 2 || a.W < 2 || (long)a.H * a.W > 0x3fffffL) return -1;
+    if (a.res) hipLaunchKernelGGL(vpt_conv_bwd_prep_anyw_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(vpt_conv_bwd_prep_anyw_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(vpt_conv_bwd_finish_kernel, dim3((unsigned)fin_blocks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(vpt_conv_bwd_sum_kernel, dim3((2 * 9 * a.CB * 32 + 255) / 256), dim3(256), 0, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+  }
+  if (!a.dy && (!a.dpooled || !a.argmax || (a.H & 1) || (a.W & 1))) return -1;
+  a.wshift = 31 - __builtin_clz((unsigned)a.W);
   if (a.gate_u) hipLaunchKernelGGL((vpt_conv_bwd_prep_kernel<true, false, true>), dim3((unsigned)grid), dim3(256), 0, stream, a);
   else if (a.dy) {
     if (a.res) hipLaunchKernelGGL((vpt_conv_bwd_prep_kernel<true, true>), dim3((unsigned)grid), dim3(256), 0, stream, a);
@@ -789,7 +862,6 @@ extern "C" int vpt_conv_bwd_prep_launch(const VptConvBwdPrepArgs* a0, hipStream_
     if (a.res) hipLaunchKernelGGL((vpt_conv_bwd_prep_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((vpt_conv_bwd_prep_kernel<false, false>), dim3((unsigned)grid), dim3(256), 0, stream, a);
   }
-  const int fin_blocks = (a.frames + 3) / 4 + ((9 * a.CB * 32 + 255) / 256) * ((a.frames + FIN_FB - 1) / FIN_FB);
   hipLaunchKernelGGL(vpt_conv_bwd_finish_kernel, dim3((unsigned)fin_blocks), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(vpt_conv_bwd_sum_kernel, dim3((2 * 9 * a.CB * 32 + 255) / 256), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? 0 : -3;
