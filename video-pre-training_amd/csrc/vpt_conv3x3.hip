@@ -1,43 +1,44 @@
-// 3x3 / pad-1 convolution of the IMPALA residual CNN as an implicit GEMM on bf16 MFMA (gfx950).
+// 3x3 / pad-1 convolution of the IMPALA residual CNN as an implicit GEMM on 16-bit MFMA (gfx950): forward and dgrad.
 //
 // Replaces, per call:  FanInInitReLULayer.forward (lib/util.py:75-82) with GroupNorm(1,C) -> Conv2d(3x3,
 // pad 1, no bias) -> ReLU, as used by CnnBasicBlock.conv0/conv1 (lib/impala_cnn.py:30-52) and by the
 // firstconv of stacks 1..2 (lib/impala_cnn.py:86-97), plus the residual add of CnnBasicBlock.forward.
 //
-// Layout in HBM: activations are channel-blocked NHWC, [frame][C/32][H][W][32] bf16, so that the 18-pixel
+// Layout in HBM: activations are channel-blocked NHWC, [frame][C/32][H][W][32] 16-bit, so that the 18-pixel
 // halo row of one 32-channel block is one contiguous 1152-byte run.  Weights are pre-packed (host side)
-// as [ntile][C_in/32][tap][128 couts][32 cin] bf16 with the GroupNorm gain folded in and the four 16-byte
+// as [ntile][C_in/32][tap][128 couts][32 cin] with the GroupNorm gain folded in and the four 16-byte
 // chunks of every 64-byte row XOR-swizzled by ((cout >> 2) & 3), i.e. already in their LDS image.
 //
 // GroupNorm fold: conv(W, (x-mu)*rstd*g + b) with zero padding applied AFTER the norm equals
 //     rstd * conv(W*g, x)  -  rstd*mu * SG[e][o]  +  SA[e][o]
 // where SG/SA sum W*g / W*b over the taps that are inside the image for the pixel's edge class e
-// (3 row classes x 3 column classes).  The main loop therefore streams raw bf16 activations; the
+// (3 row classes x 3 column classes).  The main loop therefore streams raw 16-bit activations; the
 // per-frame statistics (sum, sum of squares; produced by the previous kernel's epilogue) enter only
 // in the epilogue.
 //
-// Tiling: one workgroup (4 waves) = 16x16 output pixels x 128 output channels of one frame; wave tile
-// 128 px x 64 couts = 4x2 MFMA 32x32x16 accumulators.  K loop: for each 32-channel block the 18x18x32
-// halo tile is register-staged into LDS once (zero-filled outside the image) and reused by all nine taps;
-// the weight tile of one kernel row (3 taps, 24 KB) is DMA'd global->LDS (global_load_lds, no VGPRs, no
-// ds_write) into a double buffer one step ahead, so a step costs ONE barrier.  round-1 profile: the first
-// version of this kernel was LDS-bound (SQ_LDS_IDX_ACTIVE > MFMA busy, 39 % of it bank conflicts); hence
-//   - the weight image is swizzled so ds_read_b128 of B fragments is conflict-free on 64-byte rows,
-//   - the 32 rows of an MFMA M-subtile map to pixels so that every hardware 16-lane ds_read_b128 group
-//     covers 16 consecutive pixels of ONE image row (80-byte pixel stride -> 16 distinct bank slots),
-//   - halo ds_write_b128 are ordered so each 8-lane group hits 8 distinct 16-byte slots.
-// Two workgroups per CU (78.6 KB LDS, <= 256 VGPRs) hide each other's barriers and epilogues.
-// The FORWARD modes run the same tile on v_mfma_f32_16x16x32 (8 pixel rows x 4 cout groups of 16x16 accumulators per wave) with an epilogue in
-// the accumulators' own layout -- see M16 in the kernel; what is said above about fragments and the epilogue describes the dgrad modes.
+// What every mode of vpt_conv3x3_kernel shares:
+//   - Tile: one workgroup (4 waves: 2 row groups x 2 channel halves) = 16x16 output pixels x 128 output channels of one frame; a wave
+//     owns 128 pixels x 64 couts.  Two workgroups per CU (78.6 KB LDS each, <= 256 VGPRs) hide each other's barriers and epilogues.
+//   - LDS plan: [halo 18x18 pixels x 80-byte pitch][2 x 24 KB weight buffers][epilogue constant table 9 edge classes x 128 couts]
+//     [block statistics][mode 5's residual bias].  Per 32-channel block the halo tile is register-staged into LDS once (zero-filled
+//     outside the image) and reused by all nine taps.
+//   - K step = one kernel row (3 taps) of one 32-channel block.  Its 24 KB weight tile is DMA'd global -> LDS (global_load_lds: no
+//     VGPRs, no ds_write) into the double buffer one step ahead, so a step costs ONE barrier; the wait in front of the barrier is a
+//     counted s_waitcnt that retires the DMA only and leaves the younger halo / residual loads in flight.
+//   - The instruction order of a step is written out and pinned with sched_barrier (macros CONV_STEP / CONV_STEP16).
+// Forward modes (0, 1, 4, 5, 7): v_mfma_f32_16x16x32 main loop (8 pixel rows x 4 cout groups of 16x16 accumulators per wave), epilogue
+//   in the accumulators' own layout -- 16-byte loads and stores per lane, no lane exchange.  Halo records of odd pixels are shifted by
+//   16 bytes so that fragment reads and halo writes are bank-conflict-free (see FWD16 in the kernel).
+// Dgrad modes (2, 3, 6): v_mfma_f32_32x32x16 main loop (4x2 accumulators of 32x32 per wave; the 32 rows of an M-subtile map to pixels
+//   by sub_row() so that every hardware 16-lane ds_read_b128 group covers 16 consecutive pixels of ONE image row), epilogue through
+//   v_permlane32_swap / v_permlane16_swap into whole 128-byte lines.
+// How the kernel got here (the measurements behind each of these choices): DESIGN.md section 4, docs/history/, profiles/.
 #include "vpt_common.h"
 #include "vpt_kernels.h"
 #include <stdlib.h>
 #include <type_traits>
 #ifndef VPT_EPI_NO_CLAMP_RELU
 #define VPT_EPI_NO_CLAMP_RELU 0   // A/B builds: 1 = residual modes with the fp32 v_max ReLU of rounds 1-4 (bit-identical outputs)
-#endif
-#ifndef VPT_EPI_ABLATE
-#define VPT_EPI_ABLATE 0   // profiling builds: 1 = no output stores, 2 = no residual loads inside the epilogue, 4 = no residual prefetch in the main loop (registers uninitialised)
 #endif
 // Profiling switches (VPT_CONV_ABLATE = 1: skip the epilogue, 2: skip the main loop; VPT_CONV_EXTRA_LDS: dynamic LDS to force one
 // workgroup per CU) exist ONLY in builds made with -DVPT_CONV_PROFILE (tools/build_variant.sh): the shipped library reads no
@@ -46,10 +47,6 @@
 #define CONV_ABLATE (a.ablate)
 #else
 #define CONV_ABLATE 0
-#endif
-
-#ifndef VPT_CONV_MFMA16
-#define VPT_CONV_MFMA16 1   // 1: the forward modes run their main loop on v_mfma_f32_16x16x32 (see M16 in the kernel); 0: every mode on 32x32x16
 #endif
 #define A_RS 80
 #define A_BYTES (324 * A_RS)            // 25920
@@ -65,10 +62,7 @@ static_assert(256 * PT_RS <= KK_OFF, "the pooled mode's output tile must fit bel
 // 4..11 so that each 16-lane ds_read_b128 group {0-3,12-15,20-27} / {4-11,16-19,28-31} stays in one image row.
 __device__ __forceinline__ int sub_row(int i) { return ((i >> 4) ^ (i >> 2) ^ (i >> 3)) & 1; }
 
-
-// The wait in front of each step's barrier is a counted s_waitcnt that retires the weight DMA only and leaves the younger
-// halo / residual prefetch loads in flight across the barrier (a plain __syncthreads() drains vmcnt to 0 because an LDS-DMA
-// is pending).
+// Template parameters of vpt_conv3x3_kernel:
 // TRACE (tools/conv_trace.py): phase timestamps.  Compile time because s_memrealtime is a scalar-memory operation: one of them
 // in flight makes lgkmcnt out of order and every LDS wait of the epilogue degenerates to lgkmcnt(0).
 // MODE (compile time, so the epilogue carries no runtime branches): 0 forward, 1 forward + residual,
@@ -76,13 +70,13 @@ __device__ __forceinline__ int sub_row(int i) { return ((i >> 4) ^ (i >> 2) ^ (i
 // lib/impala_cnn.py:114-117: firstconv -> max_pool2d): the 16 x 16 output tile goes to LDS instead of HBM, its 8 x 8 pooled pixels are
 // written -- complete where the 3 x 3 window lies inside the tile, the in-tile part of the maximum on the tile's first pooled row /
 // column otherwise -- together with the tile's last row and column (the "seams"); vpt_pool_seam_kernel finishes the seam pixels.
-// The pre-pool tensor (2 MB per frame in stack 1: written and read back by vpt_pool_kernel before) never reaches HBM.
-// TR (compile time): pixel rows of the workgroup's tile.  16: four waves (2 row groups x 2 channel halves), two workgroups per CU.
+// The pre-pool tensor (2 MB per frame in stack 1) never reaches HBM.  Modes 5, 6, 7: see the kernel's first lines.
+// TR (compile time, forward modes): pixel rows of the workgroup's tile.  16: four waves, two workgroups per CU.
 // 32: EIGHT waves (4 row groups x 2 channel halves) on a 32 x 16-pixel tile, one workgroup per CU -- the same waves per SIMD, the same
 // per-wave program, but the step's 24 KB weight tile is fetched ONCE for 512 pixels instead of once per co-resident workgroup: half
-// the weight DMA (288 KB per 256 pixels and K = 1152 before -- the largest stream on a CU's memory path) and
-// 11 % less halo (34 x 18 instead of 2 x 18 x 18 pixels).
-// M16 accumulators: the four 16x16 accumulators (cout groups u) of one pixel row live in ONE 16-register tuple, so the register allocator
+// the weight DMA and 11 % less halo (34 x 18 instead of 2 x 18 x 18 pixels).  Measured at parity (see the launch function).
+//
+// Forward accumulators: the four 16x16 accumulators (cout groups u) of one pixel row live in ONE 16-register tuple, so the register allocator
 // places them like the 32x32 accumulators (whole aligned blocks, no fragmentation between 4-register tuples)
 template <int U> __device__ __forceinline__ f32x4 ac_get(const f32x16& v) {
   return __builtin_shufflevector(v, v, 4 * U, 4 * U + 1, 4 * U + 2, 4 * U + 3);
@@ -129,8 +123,8 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   // [2^-86, 2^40] the result would differ from an unscaled ReLU (denormal / saturated): no GroupNorm-fed convolution output lives there.
   constexpr bool CLAMP_RELU = (MODE == 1 || MODE == 5) && !VPT_EPI_NO_CLAMP_RELU;
   constexpr float RELU_S = CLAMP_RELU ? 0x1p-40f : 1.f, RELU_INV = 0x1p40f;
-  constexpr bool BWD = (MODE == 2 || MODE == 3 || MODE == 6), HAS_RES = (MODE == 1 || MODE == 3 || MODE == 5), USE_X = BWD, POOL = (MODE == 4 || MODE == 7), RES_AFF = MODE == 5;
-  // M16 (forward modes): main loop on v_mfma_f32_16x16x32.  Wave tile 8 pixel rows x 64 couts = 8 x 4 accumulators of 16 pixels x 16 couts;
+  constexpr bool BWD = (MODE == 2 || MODE == 3 || MODE == 6), HAS_RES = (MODE == 1 || MODE == 3 || MODE == 5), POOL = (MODE == 4 || MODE == 7), RES_AFF = MODE == 5;
+  // FWD16 (forward modes): main loop on v_mfma_f32_16x16x32.  Wave tile 8 pixel rows x 64 couts = 8 x 4 accumulators of 16 pixels x 16 couts;
   // weights are the A operand, pixels the B operand, one ds_read_b128 per fragment carries the whole K = 32 of a tap.
   //   - halo image: the 64-byte record of halo pixel P starts at 80 P + 16 (P & 1) -- odd pixels use the pitch's pad chunk in FRONT -- and MFMA
   //     column c holds pixel pcol(c) of the row: the even pixels on lanes {0-3, 12-15}, the odd ones on {4-11}.  The hardware serves a
@@ -142,23 +136,21 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   //     32-cout block give lane (c, q) couts 8 q .. 8 q + 7: 16 contiguous bytes of its pixel's record.  Under the packed image's swizzle
   //     ((cout >> 2) & 3) the four rows of one bank class (r & 3) read chunk positions q0 ^ s, (q0 + 1) ^ (s + 2), (q0 + 1) ^ s, q0 ^ (s + 2)
   //     (s = b) in a hardware lane group: all four, conflict-free, the swizzle stays as it is.
-  constexpr bool M16 = VPT_CONV_MFMA16 && (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 5 || MODE == 7);
+  constexpr bool FWD16 = (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 5 || MODE == 7);
+  static_assert(FWD16 == !BWD, "forward modes: 16x16x32 loop and native-layout epilogue; dgrad modes: 32x32x16 loop and lane-swap epilogue");
+  static_assert(!POOL || FWD16, "the pool-fused epilogue reads the 16x16 accumulators");
   constexpr bool DEFER_STORES = MODE != 3;   // mode 3 holds skip + xin pieces as well: no registers left for the packed results
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_SZ];
   const int tid = threadIdx.x, lane = tid & 63;
   // profiling (vpt_conv3x3_set_trace): CU id + 100 MHz timestamps of the tile's phases
   int cu_key = -1;
   long long t_trace[3];
-  if (TRACE && (M16 || tid == 0)) {   // (M16: wave-uniform, so the stamps stay in scalar registers across the main loop)
+  if (TRACE && (FWD16 || tid == 0)) {   // (FWD16: wave-uniform, so the stamps stay in scalar registers across the main loop)
     t_trace[0] = wall_clock64();
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID: cu_id[11:8] sh_id[12] se_id[15:13]
     const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_XCC_ID[3:0]
     cu_key = (int)(((xcc & 15u) << 8) | ((hw >> 8) & 0xffu));
   }
-#ifdef VPT_CONV_DEPHASE   // profiling builds: the SECOND workgroup of a CU's first generation (wave slot 1 of its SIMD) starts VPT_CONV_DEPHASE x ~4 us late
-  if (blockIdx.x < 512 && (__builtin_amdgcn_s_getreg((4 << 11) | 4) & 15u) == 1u)
-    for (int i_ = 0; i_ < VPT_CONV_DEPHASE; ++i_) __builtin_amdgcn_s_sleep(127);
-#endif
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = w >> 1, wn = w & 1;
   const int hi = lane >> 5, l31 = lane & 31;
@@ -179,15 +171,15 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
 #pragma unroll
   for (int m = 0; m < NA; ++m) {
     const int q = tid + NTHR * m;
-    // M16: the 8 lanes of a ds_write_b128 group carry 4 pixels of one parity x 2 parts (slots 2 k + part + const mod 8: all eight)
-    const int P = M16 ? ((q >> 5) << 3) + 2 * (q & 3) + ((q >> 4) & 1) : ((q >> 5) << 3) + (q & 7);
-    const int part = M16 ? 2 * ((q >> 3) & 1) + ((q >> 2) & 1) : (q >> 3) & 3;
+    // FWD16: the 8 lanes of a ds_write_b128 group carry 4 pixels of one parity x 2 parts (slots 2 k + part + const mod 8: all eight)
+    const int P = FWD16 ? ((q >> 5) << 3) + 2 * (q & 3) + ((q >> 4) & 1) : ((q >> 5) << 3) + (q & 7);
+    const int part = FWD16 ? 2 * ((q >> 3) & 1) + ((q >> 2) & 1) : (q >> 3) & 3;
     a_loff[m] = -1;
     a_gbyte[m] = 0u;
     if (P < HPIX) {
       const int hy = P / 18, hx = P - hy * 18;
       const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
-      a_loff[m] = P * A_RS + part * 16 + (M16 ? 16 * (P & 1) : 0);
+      a_loff[m] = P * A_RS + part * 16 + (FWD16 ? 16 * (P & 1) : 0);
       if (y >= 0 && y < a.H && x >= 0 && x < a.W) {
         a_gbyte[m] = (unsigned)((y * a.W + x) * 32 + part * 8) * 2u;
         a_inside |= 1u << m;
@@ -195,17 +187,23 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     }
   }
   const op16_t* xplane = a.x + (size_t)f * NCB * HW * 32;
-  // M16: chunk m of a thread lies NTHR / 4 halo pixels behind chunk m - 1 (same parity, same part): ONE address register and constant
+  // FWD16: chunk m of a thread lies NTHR / 4 halo pixels behind chunk m - 1 (same parity, same part): ONE address register and constant
   // offsets; only the last chunk can fall beyond the halo
   constexpr int H16_STR = (NTHR / 4) * A_RS;
   static_assert(((NA - 2) * NTHR + NTHR - 1) / 32 * 8 + 7 < HPIX, "all chunks but a thread's last are inside the halo");
   const int a_l0 = a_loff[0];
   const bool a_lastok = a_loff[NA - 1] >= 0;
-#define HALO_WR16(m_) do { if ((m_) < NA - 1 || a_lastok) *(u32x4*)(smem + a_l0 + (m_) * H16_STR) = ((a_inside >> (m_)) & 1u) ? areg[m_] : zero4; } while (0)
   // weight DMA: wave w moves pieces (NWAVE*m + w), m = 0..NDMA-1, of the 24 KB step tile; lane = 16-byte chunk
   const op16_t* wbase = a.wpk + (size_t)nt * NCB * 9 * 4096 + (size_t)(w * 64 + lane) * 8;
   unsigned char* bdst = smem + A_SZ + w * 1024;
 
+  // ====================================================================================================================
+  // Macros of BOTH main loops.  (All macros of the kernel are defined here, in three sections, and undefined together behind the epilogue
+  // dispatch; they expand where they are used, so the names they mention are declared further down.)
+  // ====================================================================================================================
+#define SB() __builtin_amdgcn_sched_barrier(0)
+#define NOP_() ((void)0)
+  // weight DMA of one step (global -> LDS, no registers): ISSUE_B = all of a wave's pieces at once (prologue), GLDS = one piece in a slot of the loop
 #define ISSUE_B(step_, buf_)                                                                              \
   do {                                                                                                    \
     const op16_t* wp_ = wbase + (size_t)(step_) * 12288;                                                  \
@@ -214,173 +212,42 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
                                        (__attribute__((address_space(3))) void*)(bdst + (buf_) * B_BYTES + m_ * (NWAVE * 1024)), \
                                        16, 0, 0);                                                         \
   } while (0)
+#define GLDS(m_)                                                                                          \
+  do { if ((m_) < NDMA)                                                                                   \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wp_ + (m_) * (NWAVE * 512)),    \
+                                   (__attribute__((address_space(3))) void*)(bd_ + (m_) * (NWAVE * 1024)), 16, 0, 0); } while (0)
+  // halo chunk m_ of the next channel block, into its staging register
+#define XA(m_) do { if ((m_) < NA) areg[m_] = *(const u32x4*)((const char*)xplane + (cbo_ + a_gbyte[m_])); } while (0)
+  // The wait in front of a step's barrier is a COUNTED s_waitcnt: it retires the weight DMA and leaves the younger halo / residual loads in
+  // flight across the barrier (a plain __syncthreads() drains vmcnt to 0 because an LDS-DMA is pending).  Memory operations are therefore
+  // issued in a FIXED order and count per wave -- weight DMA (NDMA), then either the halo of the next block (NA, PRE_A) or, in the modes with
+  // a residual, the first pieces of it (PRE_R).  Every counted load must be LIVE (a load whose result is unused is deleted by the compiler and
+  // the count would then release the barrier early -- this bit once: the residual prefetch of a residual-free instantiation), hence the
+  // compile-time HAS_RES in the steps.
+#define WAIT_BARRIER(n_late_)                                                                             \
+  do {                                                                                                    \
+    asm volatile("s_waitcnt vmcnt(" #n_late_ ") lgkmcnt(0)" ::: "memory");                                \
+    __builtin_amdgcn_s_barrier();                                                                         \
+    asm volatile("" ::: "memory");                                                                        \
+    SB();                                                                                                 \
+  } while (0)
 
-  u32x4 areg[NA];
-  const u32x4 zero4 = {0u, 0u, 0u, 0u};
-
-  // ---- prologue: weights of step 0 (DMA), halo of channel block 0, epilogue constant table ----
-  ISSUE_B(0, 0);
-#pragma unroll
-  for (int m = 0; m < NA; ++m) areg[m] = *(const u32x4*)((const char*)xplane + a_gbyte[m]);
-  float mean = 0.f, rstd = 1.f, c0f = 0.f, c1f = 0.f;
-  const float* esa = a.edge_sa;
-  if (!BWD) {
-    if (a.kk_frame) {   // the epilogue table of THIS frame was prepared by vpt_nfold_coef_kernel (the input is a pooled tensor whose GroupNorm `n`
-      rstd = a.rs_frame[f];                               // is folded into this layer): out = relu(rs * acc + kk_frame[f][e][o])
-      esa = a.kk_frame + (size_t)f * 9 * a.CoutPad;
-    } else {
-      frame_mean_rstd(a.stats_in, f, a.inv_count_in, mean, rstd);
-    }
-  } else if (a.coef) {
-    c0f = a.coef[2 * f];
-    c1f = a.coef[2 * f + 1];
-  }
-  if constexpr (M16) {   // wave-uniform, but computed by vector instructions: held in a scalar register across the main loop
-    rstd = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rstd)));
-    mean = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mean)));
-  }
-  float rgate = 1.f;
-  if (GATE) {      // everything the epilogue adds is linear in the scale: fold rstd0 into the coefficients
-    float mg;
-    frame_mean_rstd(a.gate_stats, f, a.inv_count_gate, mg, rgate);
-    c0f *= rgate;
-    c1f *= rgate;
-  }
-  {
-    float* kk = (float*)(smem + KK_O);
-    float ksa[NKK], ksg[NKK];
-#pragma unroll
-    for (int k = 0; k < NKK; ++k) {  // 9*128 = 4.5 * 256 entries: all the loads in flight together
-      const int idx = tid + NTHR * k;
-      const int o = (idx >> 7) * a.CoutPad + nt * 128 + (idx & 127);
-      ksa[k] = (idx < 9 * 128 && !BWD) ? esa[o] : 0.f;
-      ksg[k] = (idx < 9 * 128 && !BWD) ? a.edge_sg[o] : 0.f;
-    }
-#pragma unroll
-    for (int k = 0; k < NKK; ++k) {
-      const int idx = tid + NTHR * k;
-      if (idx < 9 * 128) kk[idx] = (ksa[k] - rstd * mean * ksg[k]) * RELU_S;
-    }
-  }
-  float res_s = 1.f;
-  if (RES_AFF) {
-    res_s = a.res_scale[f];
-    if (tid < 128) ((float*)(smem + BT_O))[tid] = (nt * 128 + tid < a.Cout) ? a.res_bias[(size_t)f * a.Cout + nt * 128 + tid] : 0.f;
-  }
+  // ====================================================================================================================
+  // Macros of the DGRAD loop (modes 2, 3, 6): v_mfma_f32_32x32x16, wave tile 128 px x 64 couts = acc[4][2], lane-swap epilogue.
+  // One K step = one kernel row (3 taps) of one 32-channel block = 6 groups (tap dx, 16-channel half ks) of 8 MFMAs per wave.  The schedule
+  // is explicit, one instruction pair at a time, pinned with sched_barrier (left alone, the scheduler sinks every fragment read next to its
+  // first use to save registers, and the matrix pipe drains for one LDS round trip per group):
+  //   - two fragment register sets; while group g's MFMAs issue, the fragments of group g+1 are requested, one pair of ds_read_b128 behind
+  //     each of the first three MFMAs, in the order the next group consumes them;
+  //   - the two remaining slots of each group carry the step's global traffic: the weight DMA of the next step (6 x global_load_lds, groups
+  //     0-2) and the halo of the next channel block / the residual (groups 3-4), so no MFMA ever queues behind a burst of memory instructions;
+  //   - the step's barrier sits in front of the LAST group's MFMAs: every wave then holds its last fragments of the step in registers, the
+  //     next step's weights (requested >= 24 MFMAs earlier) have landed, so the next step's first fragments are requested behind the barrier
+  //     and arrive under group 5's MFMAs.
+  // ====================================================================================================================
 #define WRITE_HALO()                                                                                      \
   _Pragma("unroll") for (int m_ = 0; m_ < NA; ++m_)                                                       \
     if (a_loff[m_] >= 0) *(u32x4*)(smem + a_loff[m_]) = ((a_inside >> m_) & 1u) ? areg[m_] : zero4
-  if constexpr (M16) {
-#pragma unroll
-    for (int m = 0; m < NA; ++m) HALO_WR16(m);
-  } else {
-    WRITE_HALO();
-  }
-  __syncthreads();
-
-  f32x16 acc[4][2];
-  f32x16 ac[8];              // M16: [pixel row j of the wave's 8], elements 4 u .. 4 u + 3 = cout group u (ac_get / ac_set)
-  f32x16 zero16;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-
-  // fragment base addresses
-  const unsigned char* aL = smem + ((wm * 8 + sub_row(l31)) * 18 + (l31 & 15)) * A_RS + hi * 16;
-  const int bsw = (l31 >> 2) & 3;
-  const unsigned char* bL0 = smem + A_SZ + (wn * 64 + l31) * 64 + (((0 + hi) ^ bsw) << 4);  // ks = 0
-  const unsigned char* bL1 = smem + A_SZ + (wn * 64 + l31) * 64 + (((2 + hi) ^ bsw) << 4);  // ks = 1
-
-  // M16 fragment bases: lane = (MFMA column / row c16, K chunk q16)
-  const int c16 = lane & 15, q16 = lane >> 4;
-  const int pcol = (c16 < 4) ? 2 * c16 : ((c16 < 12) ? 2 * (c16 - 4) + 1 : 2 * (c16 - 8));   // pixel column of MFMA column c16
-  // (LDS pointers the compiler cannot see behind: every fragment read is base + a 16-bit immediate; folded into the array's address the larger
-  // offsets no longer fit the instruction and each costs an address register)
-  typedef const __attribute__((address_space(3))) unsigned char* lds_cptr;
-  lds_cptr aLe = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (pcol & 1);        // taps dx = 0, 2: halo pixel parity = pcol's
-  lds_cptr aLo = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (1 - (pcol & 1));  // tap dx = 1
-  // cout group u = 2 blk + b: row 32 blk + 8 (c16 >> 2) + 4 b + (c16 & 3), swizzle ((row >> 2) & 3) = (2 (c16 >> 2) + b) & 3
-  lds_cptr bW0 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2)) & 3)) << 4);
-  lds_cptr bW1 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + 4 + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2) + 1) & 3)) << 4);
-  if constexpr (M16) { asm volatile("" : "+v"(aLe), "+v"(aLo), "+v"(bW0), "+v"(bW1)); }
-
-  // epilogue addressing (needed early: the residual is requested during the last channel block)
-  // Operands are SWAPPED in the MFMA (weights = A rows, pixels = B columns): a lane holds ONE pixel (column l31 of the
-  // 2x16-pixel subtile) and, per accumulator, four groups g of 4 consecutive output channels 8g + 4hi .. +3 -- 8 bytes of
-  // the pixel's 64-byte channel row per group, the partner lane (l31, 1 - hi) holding the 8 bytes next to them.  One
-  // v_permlane32_swap per dword turns the pair (g = 2p, 2p + 1) into 16 CONTIGUOUS bytes per lane (lower half-wave: bytes
-  // 32p.., upper: 32p + 16..), and one v_permlane16_swap per dword (lanes l <-> l ^ 16, p = 0 <-> 1) regroups those so that one
-  // 16-byte access per lane covers the WHOLE 64-byte channel row of 16 pixels: the residual / xin / output move as complete
-  // 128-byte lines, with no LDS staging at all.  (Round 1 staged them through a wave-private LDS tile: four LDS round trips
-  // per subtile that queued behind the co-resident workgroup's main-loop LDS traffic.  The first LDS-free version moved 32
-  // bytes per pixel and instruction, so every line was touched by two instructions; an ablation without the output stores ran
-  // 6-14 % faster, whole-line stores recovered 2-4.4 % of that.)
-  const int CB_out = a.Cout >> 5;
-  const int cb0 = nt * 4 + wn * 2;                 // 32-channel block of n2 = 0
-  const bool nvalid[2] = {(cb0 + 0) < CB_out, (cb0 + 1) < CB_out};
-  // Addresses = wave-uniform base (frame, channel block n2) + a 32-bit per-lane byte offset: global accesses with an SGPR
-  // base, no 64-bit vector address arithmetic, no address registers kept across the main loop.
-  const unsigned gm_b = (unsigned)(2 * a.W) * 64u;   // + m * gm_b: two image rows further down (bytes)
-  // instruction j = 0 / 1 of a pair carries the 64-byte rows of the pixels held by lanes (l31 & 15) + 16 j; this lane supplies
-  // (receives) bytes 32 (l31 >> 4) + 16 hi .. + 15 of them
-  unsigned svoff[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-    svoff[j] = (unsigned)(((ty0 + wm * 8 + sub_row((l31 & 15) + 16 * j)) * a.W + tx0 + (l31 & 15)) * 32 + 16 * (l31 >> 4) + 8 * hi) * 2u;
-  size_t cbase[2];                                  // element offset of channel block n2 of this frame
-#pragma unroll
-  for (int n2 = 0; n2 < 2; ++n2) cbase[n2] = (size_t)(f * CB_out + (nvalid[n2] ? cb0 + n2 : 0)) * HW * 32;
-#define EPI_LD(ptr_, m_, n2_, p_) (*(const u32x4*)((const char*)((ptr_) + cbase[n2_]) + (svoff[p_] + (unsigned)(m_) * gm_b)))
-#ifndef VPT_RES_LATE
-#define VPT_RES_LATE 0     // 1: the residual prefetch rides in the tile's last-but-one step (see the last channel block below); 0: one step earlier (rounds 2-4).  Measured: +1.8 % on s0.block alone, nothing on the step (profiles/r04_experiments.md section 15)
-#endif
-#ifndef VPT_RES_PREFETCH
-#define VPT_RES_PREFETCH 1   // 0: no residual request inside the main loop; all four subtiles are requested at the start of the epilogue
-#endif
-#ifndef VPT_RES_NATIVE
-#define VPT_RES_NATIVE 1   // 1: the residual arrives in the accumulators' own layout (8-byte loads: a lane's 4 channels of a group), no lane exchanges;
-#endif                     // 0: whole 128-byte lines per 16-byte load + v_permlane16/32_swap (round 2-3; the output stores still go that way)
-#if VPT_RES_NATIVE
-  // Round 4 (profiles/r04_experiments.md): the residual path cost 16 % of a K = 1152 tile beyond its loads -- 128 of its 256 vector
-  // instructions were lane exchanges (43 cycles of latency each, half the issue rate of a plain instruction: tools/ubench/permlane.hip) in
-  // front of every add.  An 8-byte load per (subtile, channel block, group) puts the lane's own 4 channels where the add needs them.
-  u32x2 rq[4][2][4];                                // residual [subtile m][n2][group g]
-  const unsigned nvoff = (unsigned)(((ty0 + wm * 8 + sub_row(l31)) * a.W + tx0 + (l31 & 15)) * 32 + 4 * hi) * 2u;
-#define EPI_LDN(ptr_, m_, n2_, g_) (*(const u32x2*)((const char*)((ptr_) + cbase[n2_]) + (nvoff + (unsigned)(m_) * gm_b + 16u * (unsigned)(g_))))
-#define LOAD_RES(m_)                                                                                      \
-  _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
-    _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) rq[m_][n2_][g_] = EPI_LDN(a.res, m_, n2_, g_)
-#else
-  u32x4 rq[4][2][2];                                // residual [subtile m][n2][instruction j of the pair]
-#define LOAD_RES(m_)                                                                                      \
-  _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
-    _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_) rq[m_][n2_][p_] = EPI_LD(a.res, m_, n2_, p_)
-#endif
-  // M16: lane (c16, q16) owns bytes 16 q16 .. + 15 of pixel pcol(c16)'s 64-byte record in every (pixel row j, 32-cout block n2): residual, xin and
-  // output move as ONE 16-byte access per lane, 1024 contiguous bytes per instruction, in the accumulators' own layout.
-  const unsigned voff16 = (unsigned)(((ty0 + wm * 8) * a.W + tx0 + pcol) * 32 + 8 * q16) * 2u;
-  const unsigned gj_b = (unsigned)a.W * 64u;           // + j * gj_b: one image row further down (bytes)
-  u32x4 rq16[8][2];                                    // residual [pixel row j][n2]
-#define EPI_LD16(ptr_, j_, n2_) (*(const u32x4*)((const char*)((ptr_) + cbase[n2_]) + (voff16 + (unsigned)(j_) * gj_b)))
-#define XR16(j_) do { rq16[j_][0] = EPI_LD16(resp, j_, 0); rq16[j_][1] = EPI_LD16(resp, j_, 1); } while (0)
-
-  // ---- main loop ----------------------------------------------------------------------------------------------------
-  // One K step = one kernel row (3 taps) of one 32-channel block = 6 groups (tap dx, 16-channel half ks) of 8 MFMAs per
-  // wave.  Round-1 profile: 55 % of the wave cycles were SQ_WAIT_INST_ANY -- every group read its six fragments into the
-  // registers the previous group's MFMAs had just released and then waited lgkmcnt(0), so the matrix pipe drained for one
-  // LDS round trip per 8 MFMAs (one workgroup per CU alone reached 85 % of two).  Now the schedule is explicit, one
-  // instruction pair at a time, pinned with sched_barrier (left alone, the scheduler sinks every fragment read next to
-  // its first use to save registers):
-  //   - two fragment register sets; while group g's MFMAs issue, the fragments of group g+1 are requested, one
-  //     pair of ds_read_b128 behind each of the first three MFMAs, in the order the next group consumes them;
-  //   - the two remaining slots of each group carry the step's global traffic: the weight DMA of the next step
-  //     (6 x global_load_lds, groups 0-2) and the halo of the next channel block / the residual (groups 3-4), so no
-  //     MFMA ever queues behind a burst of memory instructions;
-  //   - the step's barrier sits in front of the LAST group's MFMAs: every wave then holds its last fragments of the
-  //     step in registers, the next step's weights (requested >= 24 MFMAs earlier) have landed, so the next step's
-  //     first fragments are requested behind the barrier and arrive under group 5's MFMAs.
-  op16x8 fa[2][4], fb[2][2];
-  const op16_t* resp = a.res;
-#define SB() __builtin_amdgcn_sched_barrier(0)
 #define MM(set_, m_, n_) acc[m_][n_] = VPT_MFMA_32X32X16(fb[set_][n_], fa[set_][m_], acc[m_][n_], 0, 0, 0)
 #define MMZ(set_, m_, n_) acc[m_][n_] = VPT_MFMA_32X32X16(fb[set_][n_], fa[set_][m_], zero16, 0, 0, 0)   /* C = 0: no zero-initialised accumulators */
 #define FA_LD(set_, dy_, g_, m_) \
@@ -405,35 +272,13 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   do {                                                                                                    \
     _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) { MM(set_, m_, 0); MM(set_, m_, 1); }                \
   } while (0)
-#ifndef VPT_CONV_HALO_ABLATE
-#define VPT_CONV_HALO_ABLATE 0  // profiling builds (wrong results, timing only): 1 = halo written without the zero-fill selects, 2 = no halo loads / writes after block 0
-#endif
-#ifndef VPT_CONV_DMA_PIECES
-#define VPT_CONV_DMA_PIECES 6   // profiling builds: fewer weight-DMA pieces per wave and step (the results are then wrong; timing only)
-#endif
-#define GLDS(m_)                                                                                          \
-  do { if ((m_) < VPT_CONV_DMA_PIECES && (m_) < NDMA)                                                     \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wp_ + (m_) * (NWAVE * 512)),    \
-                                   (__attribute__((address_space(3))) void*)(bd_ + (m_) * (NWAVE * 1024)), 16, 0, 0); } while (0)
-#define XA(m_) do { if (VPT_CONV_HALO_ABLATE != 2 && (m_) < NA) areg[(m_) < NA ? (m_) : 0] = *(const u32x4*)((const char*)xplane + (cbo_ + a_gbyte[m_])); } while (0)
-#if VPT_RES_NATIVE
+  // residual (mode 3: the skip connection) in the accumulators' own layout, 8-byte loads; xin and the output as whole 128-byte lines (EPI_LD)
+#define EPI_LD(ptr_, m_, n2_, p_) (*(const u32x4*)((const char*)((ptr_) + cbase[n2_]) + (svoff[p_] + (unsigned)(m_) * gm_b)))
+#define EPI_LDN(ptr_, m_, n2_, g_) (*(const u32x2*)((const char*)((ptr_) + cbase[n2_]) + (nvoff + (unsigned)(m_) * gm_b + 16u * (unsigned)(g_))))
+#define LOAD_RES(m_)                                                                                      \
+  _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
+    _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) rq[m_][n2_][g_] = EPI_LDN(a.res, m_, n2_, g_)
 #define XR(m_, n2_, p_) do { rq[m_][n2_][2 * (p_)] = EPI_LDN(resp, m_, n2_, 2 * (p_)); rq[m_][n2_][2 * (p_) + 1] = EPI_LDN(resp, m_, n2_, 2 * (p_) + 1); } while (0)
-#else
-#define XR(m_, n2_, p_) rq[m_][n2_][p_] = EPI_LD(resp, m_, n2_, p_)
-#endif
-#define NOP_() ((void)0)
-#define WAIT_BARRIER(n_late_)                                                                             \
-  do {                                                                                                    \
-    asm volatile("s_waitcnt vmcnt(" #n_late_ ") lgkmcnt(0)" ::: "memory");                                \
-    __builtin_amdgcn_s_barrier();                                                                         \
-    asm volatile("" ::: "memory");                                                                        \
-    SB();                                                                                                 \
-  } while (0)
-  // Memory ops are issued in a FIXED order and count per wave -- weight DMA (6), then either the halo of the next block
-  // (6, PRE_A) or, in the modes with a residual, subtiles 0 / 1 of it (8, PRE_R) -- so the counted wait in front of the barrier
-  // is exact: it retires the DMA and leaves the younger loads in flight across the barrier.  Every counted load must be LIVE
-  // (a load whose result is unused is deleted by the compiler and the count would then release the barrier early -- this
-  // bit once: the residual prefetch of a residual-free instantiation), hence the compile-time HAS_RES in the step.
 #define CONV_STEP(cb_, dy_, NEXT_DY, PRE_A, WR_A, PRE_R, LAST, FIRST)                                            \
   do {                                                                                                    \
     const int s_ = (cb_) * 3 + (dy_);                                                                     \
@@ -457,27 +302,20 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     if (PRE_A) {                                                                                          \
       GROUP(1, dy_, 4, boff_, do { XA(0); XA(1); } while (0), do { XA(2); } while (0));                   \
       GROUP(0, dy_, 5, boff_, do { XA(3); XA(4); } while (0), do { XA(5); } while (0));                   \
-      if (VPT_CONV_HALO_ABLATE == 2) WAIT_BARRIER(0); else if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5);                               \
+      if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5);                                                 \
     } else if ((PRE_R) && HAS_RES) { /* compile-time: without a residual the loads would be dead code and the count wrong */ \
       GROUP(1, dy_, 4, boff_, do { XR(0, 0, 0); XR(0, 0, 1); } while (0), do { XR(0, 1, 0); XR(0, 1, 1); } while (0)); \
       GROUP(0, dy_, 5, boff_, do { XR(1, 0, 0); XR(1, 0, 1); } while (0), do { XR(1, 1, 0); XR(1, 1, 1); } while (0)); \
-      if (VPT_RES_NATIVE) WAIT_BARRIER(16); else WAIT_BARRIER(8);   /* (two 8-byte loads per XR in the native layout) */ \
+      WAIT_BARRIER(16);   /* (two 8-byte loads per XR) */                                                \
     } else {                                                                                              \
       GROUP(1, dy_, 4, boff_, NOP_(), NOP_());                                                            \
       GROUP(0, dy_, 5, boff_, NOP_(), NOP_());                                                            \
-      /* the tile's last step issues no DMA: the residual pieces requested in the step before stay in flight across its barrier */ \
-      if ((LAST) && HAS_RES && VPT_RES_LATE && VPT_RES_PREFETCH && !(VPT_EPI_ABLATE & 4)) { if (VPT_RES_NATIVE) WAIT_BARRIER(16); else WAIT_BARRIER(8); }  \
-      else WAIT_BARRIER(0);                                                                               \
+      WAIT_BARRIER(0);                                                                                    \
     }                                                                                                     \
     if (WR_A) {   /* the halo of the next channel block replaces the current one: second barrier before its first read */ \
       _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) {                                                  \
-        if (VPT_CONV_HALO_ABLATE == 0) {                                                                  \
-          if (a_loff[m_] >= 0) *(u32x4*)(smem + a_loff[m_]) = ((a_inside >> m_) & 1u) ? areg[m_] : zero4; \
-          if (m_ + 4 < NA && a_loff[m_ + 4 < NA ? m_ + 4 : 0] >= 0) *(u32x4*)(smem + a_loff[m_ + 4 < NA ? m_ + 4 : 0]) = ((a_inside >> (m_ + 4)) & 1u) ? areg[m_ + 4 < NA ? m_ + 4 : 0] : zero4; \
-        } else if (VPT_CONV_HALO_ABLATE == 1) {                                                           \
-          if (a_loff[m_] >= 0) *(u32x4*)(smem + a_loff[m_]) = areg[m_];                                   \
-          if (m_ + 4 < NA && a_loff[m_ + 4 < NA ? m_ + 4 : 0] >= 0) *(u32x4*)(smem + a_loff[m_ + 4 < NA ? m_ + 4 : 0]) = areg[m_ + 4 < NA ? m_ + 4 : 0];         \
-        }                                                                                                 \
+        if (a_loff[m_] >= 0) *(u32x4*)(smem + a_loff[m_]) = ((a_inside >> m_) & 1u) ? areg[m_] : zero4; \
+        if (m_ + 4 < NA && a_loff[m_ + 4] >= 0) *(u32x4*)(smem + a_loff[m_ + 4]) = ((a_inside >> (m_ + 4)) & 1u) ? areg[m_ + 4] : zero4; \
         SB(); MM(1, m_, 0); SB();                                                                         \
       }                                                                                                   \
       WAIT_BARRIER(0);                                                                                    \
@@ -491,14 +329,34 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       GROUP(1, NEXT_DY, 0, noff_, NOP_(), NOP_());                                                        \
     }                                                                                                     \
   } while (0)
+  // epilogue: the forward layer's input one subtile ahead, and the lane exchanges between "whole pixel rows" and the accumulator layout
+#define LOAD_XIN(m_)                                                                                      \
+  _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
+    _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_) xq[(m_) & 1][n2_][p_] = EPI_LD(a.xin, m_, n2_, p_)
+  // rows arrive per instruction j as the pixels of lanes (l31 & 15) + 16 j; the exchange gives every lane the two 16-byte pieces (p = 0, 1) of its own pixel
+#define ROWS_TO_PIECES(src_, dst_)                                                                        \
+  _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                                      \
+    const auto sw_ = __builtin_amdgcn_permlane16_swap((src_)[0][j_], (src_)[1][j_], false, false);        \
+    (dst_)[0][j_] = sw_[0]; (dst_)[1][j_] = sw_[1];                                                       \
+  }
+  // 16-byte piece {first half x, y | second half z, w} of a lane pair -> this lane's own 8 bytes of group 2p (e) and 2p + 1 (o)
+#define UNSWAP(v_, e_, o_)                                                                                \
+  do {                                                                                                    \
+    const auto s0_ = __builtin_amdgcn_permlane32_swap((v_).x, (v_).z, false, false);                      \
+    const auto s1_ = __builtin_amdgcn_permlane32_swap((v_).y, (v_).w, false, false);                      \
+    (e_).x = s0_[0]; (o_).x = s0_[1]; (e_).y = s1_[0]; (o_).y = s1_[1];                                   \
+  } while (0)
 
-  // ---- M16 main loop: one K step = 3 taps x 4 cout groups x 8 pixel rows = 96 MFMAs of 16x16x32 per wave, in 12 groups of 8 (one cout
-  // group over the 8 pixel rows).  Registers: the 8 pixel fragments of the CURRENT tap (32) + a double-buffered weight fragment (8) = 40.
-  // A group requests the weight fragment of the next group behind its first MFMA; the tap's last group also refills each pixel fragment for
-  // the next tap right behind the MFMA that used it last.  Vector-memory operations keep the order and count of the 32x32 loop (weight DMA,
-  // then halo / residual), one slot per group; the step's barrier sits in front of its LAST group, which holds every fragment it needs and
-  // requests the next step's first ones behind the barrier.
-  op16x8 fp[8], fw[2];
+  // ====================================================================================================================
+  // Macros of the FORWARD loop (modes 0, 1, 4, 5, 7): v_mfma_f32_16x16x32, wave tile 8 pixel rows x 4 cout groups = ac[8], epilogue in the
+  // accumulators' own layout.  One K step = 3 taps x 4 cout groups x 8 pixel rows = 96 MFMAs per wave, in 12 groups of 8 (one cout group
+  // over the 8 pixel rows).  Registers: the 8 pixel fragments of the CURRENT tap (32) + a double-buffered weight fragment (8) = 40.  A group
+  // requests the weight fragment of the next group behind its first MFMA; the tap's last group also refills each pixel fragment for the next
+  // tap right behind the MFMA that used it last.  Vector-memory operations keep the order and count of the dgrad loop (weight DMA, then halo /
+  // residual), one slot per group; the step's barrier sits in front of its LAST group, which holds every fragment it needs and requests the
+  // next step's first ones behind the barrier.
+  // ====================================================================================================================
+#define HALO_WR16(m_) do { if ((m_) < NA - 1 || a_lastok) *(u32x4*)(smem + a_l0 + (m_) * H16_STR) = ((a_inside >> (m_)) & 1u) ? areg[m_] : zero4; } while (0)
 #define PA(j_, dy_, dx_) fp[j_] = *(const __attribute__((address_space(3))) op16x8*)((((dx_) & 1) ? aLo : aLe) + (((j_) + (dy_)) * 18 + (dx_)) * A_RS)
 #define WB(tap_, u_, boff_) fw[(u_) & 1] = *(const __attribute__((address_space(3))) op16x8*)((((u_) & 1) ? bW1 : bW0) + (boff_) + (tap_) * (128 * 64) + ((u_) >> 1) * (32 * 64))
 #define M16A(j_, u_) ac_set<(u_)>(ac[j_], VPT_MFMA_16X16X32(fw[(u_) & 1], fp[j_], ac_get<(u_)>(ac[j_]), 0, 0, 0))
@@ -533,6 +391,10 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     G16(MM_, 2, WB(dx_, 3, boff_), X2);                                                                   \
     G16R(MM_, WB((dx_) + 1, 0, boff_), X3, dy_, (dx_) + 1);                                               \
   } while (0)
+  // residual row j_ x 2 channel blocks: XR16 inside the main loop, XR16L (addresses re-derived behind the loop, see voff16_l) in the epilogue
+#define EPI_LD16(ptr_, j_, n2_) (*(const u32x4*)((const char*)((ptr_) + cbase[n2_]) + (voff16 + (unsigned)(j_) * gj_b)))
+#define XR16(j_) do { rq16[j_][0] = EPI_LD16(resp, j_, 0); rq16[j_][1] = EPI_LD16(resp, j_, 1); } while (0)
+#define XR16L(j_) do { rq16[j_][0] = *(const u32x4*)((const char*)(resp + cbase[0]) + (voff16_l + (unsigned)(j_) * gj_b)); rq16[j_][1] = *(const u32x4*)((const char*)(resp + cbase[1]) + (voff16_l + (unsigned)(j_) * gj_b)); } while (0)
 #define CONV_STEP16(cb_, dy_, NEXT_DY, PRE_A, WR_A, PRE_R, LAST)                                          \
   do {                                                                                                    \
     const int s_ = (cb_) * 3 + (dy_);                                                                     \
@@ -550,7 +412,7 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       G16(M16A, 0, WB(2, 1, boff_), do { XA(3); XA(4); } while (0));                                      \
       G16(M16A, 1, WB(2, 2, boff_), XA(5));                                                               \
       G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
-      if (VPT_CONV_HALO_ABLATE == 2) WAIT_BARRIER(0); else if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5); \
+      if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5);                                                 \
     } else if ((PRE_R) && HAS_RES) {                                                                      \
       TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), XR16(0), NOP_());                                             \
       G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
@@ -563,13 +425,12 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
       G16(M16A, 1, WB(2, 2, boff_), NOP_());                                                              \
       G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
-      if ((LAST) && !TRACE && HAS_RES && VPT_RES_LATE && VPT_RES_PREFETCH && !(VPT_EPI_ABLATE & 4)) WAIT_BARRIER(2); \
-      else WAIT_BARRIER(0);                                                                               \
+      WAIT_BARRIER(0);                                                                                    \
     }                                                                                                     \
     if (WR_A) {   /* the halo of the next channel block replaces the current one: second barrier before its first read */ \
       _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) {                                                  \
         HALO_WR16(m_); SB();                                                                              \
-        if (m_ + 4 < NA) HALO_WR16(m_ + 4 < NA ? m_ + 4 : 0);                                             \
+        if (m_ + 4 < NA) HALO_WR16(m_ + 4);                                                               \
         SB(); if (m_ == 0) M16A(0, 3); else if (m_ == 1) M16A(1, 3); else if (m_ == 2) M16A(2, 3); else M16A(3, 3); SB();                                                                        \
       }                                                                                                   \
       WAIT_BARRIER(0);                                                                                    \
@@ -584,9 +445,140 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       G16R(M16A, WB(0, 0, noff_), NOP_(), NEXT_DY, 0);                                                    \
     }                                                                                                     \
   } while (0)
+  // epilogue: edge class of pixel row j_ (only the wave's first / last row can touch the image border) and the constant-table prefetch
+#define EO16(j_) ((j_) == 0 ? eo_top : ((j_) == 7 ? eo_bot : 3 * 128))
+#define LOAD_KK16(c_)                                                                                     \
+  do {                                                                                                    \
+    const float* kp_ = kk16 + EO16((c_) >> 1) + ((c_) & 1) * 32;                                          \
+    kq[(c_) & 1][0] = *(const f32x4*)kp_; kq[(c_) & 1][1] = *(const f32x4*)(kp_ + 4);                     \
+  } while (0)
+  // ====================================================================================================================
 
-  if (TRACE && (M16 || tid == 0)) t_trace[1] = wall_clock64();
-  if constexpr (M16) {
+  u32x4 areg[NA];
+  const u32x4 zero4 = {0u, 0u, 0u, 0u};
+
+  // ---- prologue: weights of step 0 (DMA), halo of channel block 0, epilogue constant table ----
+  ISSUE_B(0, 0);
+#pragma unroll
+  for (int m = 0; m < NA; ++m) areg[m] = *(const u32x4*)((const char*)xplane + a_gbyte[m]);
+  float mean = 0.f, rstd = 1.f, c0f = 0.f, c1f = 0.f;
+  const float* esa = a.edge_sa;
+  if (!BWD) {
+    if (a.kk_frame) {   // the epilogue table of THIS frame was prepared by vpt_nfold_coef_kernel (the input is a pooled tensor whose GroupNorm `n`
+      rstd = a.rs_frame[f];                               // is folded into this layer): out = relu(rs * acc + kk_frame[f][e][o])
+      esa = a.kk_frame + (size_t)f * 9 * a.CoutPad;
+    } else {
+      frame_mean_rstd(a.stats_in, f, a.inv_count_in, mean, rstd);
+    }
+  } else if (a.coef) {
+    c0f = a.coef[2 * f];
+    c1f = a.coef[2 * f + 1];
+  }
+  if constexpr (FWD16) {   // wave-uniform, but computed by vector instructions: held in a scalar register across the main loop
+    rstd = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rstd)));
+    mean = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, mean)));
+  }
+  float rgate = 1.f;
+  if (GATE) {      // everything the epilogue adds is linear in the scale: fold rstd0 into the coefficients
+    float mg;
+    frame_mean_rstd(a.gate_stats, f, a.inv_count_gate, mg, rgate);
+    c0f *= rgate;
+    c1f *= rgate;
+  }
+  {
+    float* kk = (float*)(smem + KK_O);
+    float ksa[NKK], ksg[NKK];
+#pragma unroll
+    for (int k = 0; k < NKK; ++k) {  // 9*128 = 4.5 * 256 entries: all the loads in flight together
+      const int idx = tid + NTHR * k;
+      const int o = (idx >> 7) * a.CoutPad + nt * 128 + (idx & 127);
+      ksa[k] = (idx < 9 * 128 && !BWD) ? esa[o] : 0.f;
+      ksg[k] = (idx < 9 * 128 && !BWD) ? a.edge_sg[o] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < NKK; ++k) {
+      const int idx = tid + NTHR * k;
+      if (idx < 9 * 128) kk[idx] = (ksa[k] - rstd * mean * ksg[k]) * RELU_S;
+    }
+  }
+  float res_s = 1.f;
+  if (RES_AFF) {
+    res_s = a.res_scale[f];
+    if (tid < 128) ((float*)(smem + BT_O))[tid] = (nt * 128 + tid < a.Cout) ? a.res_bias[(size_t)f * a.Cout + nt * 128 + tid] : 0.f;
+  }
+  if constexpr (FWD16) {
+#pragma unroll
+    for (int m = 0; m < NA; ++m) HALO_WR16(m);
+  } else {
+    WRITE_HALO();
+  }
+  __syncthreads();
+
+  f32x16 acc[4][2];
+  f32x16 ac[8];              // FWD16: [pixel row j of the wave's 8], elements 4 u .. 4 u + 3 = cout group u (ac_get / ac_set)
+  f32x16 zero16;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
+
+  // fragment base addresses
+  const unsigned char* aL = smem + ((wm * 8 + sub_row(l31)) * 18 + (l31 & 15)) * A_RS + hi * 16;
+  const int bsw = (l31 >> 2) & 3;
+  const unsigned char* bL0 = smem + A_SZ + (wn * 64 + l31) * 64 + (((0 + hi) ^ bsw) << 4);  // ks = 0
+  const unsigned char* bL1 = smem + A_SZ + (wn * 64 + l31) * 64 + (((2 + hi) ^ bsw) << 4);  // ks = 1
+
+  // FWD16 fragment bases: lane = (MFMA column / row c16, K chunk q16)
+  const int c16 = lane & 15, q16 = lane >> 4;
+  const int pcol = (c16 < 4) ? 2 * c16 : ((c16 < 12) ? 2 * (c16 - 4) + 1 : 2 * (c16 - 8));   // pixel column of MFMA column c16
+  // (LDS pointers the compiler cannot see behind: every fragment read is base + a 16-bit immediate; folded into the array's address the larger
+  // offsets no longer fit the instruction and each costs an address register)
+  typedef const __attribute__((address_space(3))) unsigned char* lds_cptr;
+  lds_cptr aLe = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (pcol & 1);        // taps dx = 0, 2: halo pixel parity = pcol's
+  lds_cptr aLo = (lds_cptr)smem + ((wm * 8) * 18 + pcol) * A_RS + q16 * 16 + 16 * (1 - (pcol & 1));  // tap dx = 1
+  // cout group u = 2 blk + b: row 32 blk + 8 (c16 >> 2) + 4 b + (c16 & 3), swizzle ((row >> 2) & 3) = (2 (c16 >> 2) + b) & 3
+  lds_cptr bW0 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2)) & 3)) << 4);
+  lds_cptr bW1 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + 4 + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2) + 1) & 3)) << 4);
+  if constexpr (FWD16) { asm volatile("" : "+v"(aLe), "+v"(aLo), "+v"(bW0), "+v"(bW1)); }
+
+  // epilogue addressing (needed early: the residual is requested during the last channel block)
+  // Dgrad epilogue: operands are SWAPPED in the MFMA (weights = A rows, pixels = B columns): a lane holds ONE pixel (column l31 of the
+  // 2x16-pixel subtile) and, per accumulator, four groups g of 4 consecutive output channels 8g + 4hi .. +3 -- 8 bytes of
+  // the pixel's 64-byte channel row per group, the partner lane (l31, 1 - hi) holding the 8 bytes next to them.  One
+  // v_permlane32_swap per dword turns the pair (g = 2p, 2p + 1) into 16 CONTIGUOUS bytes per lane (lower half-wave: bytes
+  // 32p.., upper: 32p + 16..), and one v_permlane16_swap per dword (lanes l <-> l ^ 16, p = 0 <-> 1) regroups those so that one
+  // 16-byte access per lane covers the WHOLE 64-byte channel row of 16 pixels: the residual / xin / output move as complete
+  // 128-byte lines, with no LDS staging at all.
+  const int CB_out = a.Cout >> 5;
+  const int cb0 = nt * 4 + wn * 2;                 // 32-channel block of n2 = 0
+  const bool nvalid[2] = {(cb0 + 0) < CB_out, (cb0 + 1) < CB_out};
+  // Addresses = wave-uniform base (frame, channel block n2) + a 32-bit per-lane byte offset: global accesses with an SGPR
+  // base, no 64-bit vector address arithmetic, no address registers kept across the main loop.
+  const unsigned gm_b = (unsigned)(2 * a.W) * 64u;   // + m * gm_b: two image rows further down (bytes)
+  // instruction j = 0 / 1 of a pair carries the 64-byte rows of the pixels held by lanes (l31 & 15) + 16 j; this lane supplies
+  // (receives) bytes 32 (l31 >> 4) + 16 hi .. + 15 of them
+  unsigned svoff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+    svoff[j] = (unsigned)(((ty0 + wm * 8 + sub_row((l31 & 15) + 16 * j)) * a.W + tx0 + (l31 & 15)) * 32 + 16 * (l31 >> 4) + 8 * hi) * 2u;
+  size_t cbase[2];                                  // element offset of channel block n2 of this frame
+#pragma unroll
+  for (int n2 = 0; n2 < 2; ++n2) cbase[n2] = (size_t)(f * CB_out + (nvalid[n2] ? cb0 + n2 : 0)) * HW * 32;
+  // The skip connection of mode 3 does NOT go that way: an 8-byte load per (subtile, channel block, group) puts the lane's own 4 channels where
+  // the add needs them, without lane exchanges (43 cycles of latency each, half the issue rate of a plain instruction: tools/ubench/permlane.hip).
+  u32x2 rq[4][2][4];                                // residual [subtile m][n2][group g]
+  const unsigned nvoff = (unsigned)(((ty0 + wm * 8 + sub_row(l31)) * a.W + tx0 + (l31 & 15)) * 32 + 4 * hi) * 2u;
+  // Forward epilogue: lane (c16, q16) owns bytes 16 q16 .. + 15 of pixel pcol(c16)'s 64-byte record in every (pixel row j, 32-cout block n2): residual and
+  // output move as ONE 16-byte access per lane, 1024 contiguous bytes per instruction, in the accumulators' own layout.
+  const unsigned voff16 = (unsigned)(((ty0 + wm * 8) * a.W + tx0 + pcol) * 32 + 8 * q16) * 2u;
+  const unsigned gj_b = (unsigned)a.W * 64u;           // + j * gj_b: one image row further down (bytes)
+  u32x4 rq16[8][2];                                    // residual [pixel row j][n2]
+
+  // ---- main loop (the schedules are the CONV_STEP / CONV_STEP16 macros above) ----
+  op16x8 fa[2][4], fb[2][2];   // dgrad: two fragment register sets
+  const op16_t* resp = a.res;
+  op16x8 fp[8], fw[2];         // forward: the current tap's 8 pixel fragments, a double-buffered weight fragment
+
+  if (TRACE && (FWD16 || tid == 0)) t_trace[1] = wall_clock64();
+  if constexpr (FWD16) {
     if (CONV_ABLATE != 2) {
       WB(0, 0, 0);
 #pragma unroll
@@ -602,8 +594,8 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         CONV_STEP16(cb, 2, 0, false, true, false, false);
       }
       // (the tracing instantiations hold the phase stamps as well: no residual request inside their main loop)
-      CONV_STEP16(NCB - 1, 0, 1, false, false, !TRACE && !VPT_RES_LATE && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false);
-      CONV_STEP16(NCB - 1, 1, 2, false, false, !TRACE && VPT_RES_LATE != 0 && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false);
+      CONV_STEP16(NCB - 1, 0, 1, false, false, !TRACE, false);
+      CONV_STEP16(NCB - 1, 1, 2, false, false, false, false);
       CONV_STEP16(NCB - 1, 2, 0, false, false, false, true);
     } else {
 #pragma unroll
@@ -630,12 +622,10 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       CONV_STEP(cb, 1, 2, false, false, false, false, false);
       CONV_STEP(cb, 2, 0, false, true, false, false, false);
     }
-    // last channel block: no further halo -> request the residual of the first two subtiles instead.  A step's barrier waits for its weight DMA with
-    // a counted vmcnt, which retires everything issued BEFORE that DMA too: a residual requested in kernel row 0 is forced home by row 1's barrier (56
-    // MFMAs later, workgroup-wide); requested in row 1 behind that step's DMA (VPT_RES_LATE) nothing waits for it before the epilogue, because the last
-    // step issues no DMA.  Built and measured in round 4: +1.8 % on the K = 1152 layer's micro-benchmark, 0.1 % on the forward step -- the default stays.
-    CONV_STEP(NCB - 1, 0, 1, false, false, !VPT_RES_LATE && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false, false);
-    CONV_STEP(NCB - 1, 1, 2, false, false, VPT_RES_LATE != 0 && !(VPT_EPI_ABLATE & 4) && VPT_RES_PREFETCH, false, false);
+    // last channel block: no further halo -> kernel row 0 requests the residual of the first two subtiles instead (mode 3).  Row 1's barrier forces it
+    // home, 56 MFMAs later; requesting it in row 1 was measured and bought nothing on the step (profiles/r04_experiments.md section 15).
+    CONV_STEP(NCB - 1, 0, 1, false, false, true, false, false);
+    CONV_STEP(NCB - 1, 1, 2, false, false, false, false, false);
     CONV_STEP(NCB - 1, 2, 0, false, false, false, true, false);
   } else {
 #pragma unroll
@@ -646,33 +636,12 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
     __syncthreads();
   }
-#undef CONV_STEP
-#undef HALO_WR16
-#undef CONV_STEP16
-#undef TAP16
-#undef G16
-#undef G16R
-#undef M16A
-#undef PA
-#undef WB
-#undef WAIT_BARRIER
-#undef GROUP
-#undef GROUP_TAIL
-#undef GLDS
-#undef XA
-#undef XR
-#undef MM
-#undef MMZ
-#undef GROUP_
-#undef GROUP_Z
-#undef FA_LD
-#undef FB_LD
 
   // ---------------- epilogue ----------------
-  if (TRACE && (M16 || tid == 0)) t_trace[2] = wall_clock64();
+  if (TRACE && (FWD16 || tid == 0)) t_trace[2] = wall_clock64();
   if (CONV_ABLATE == 1) {  // profiling: keep the accumulators live, skip the epilogue
     float t = 0.f;
-    if constexpr (M16) {
+    if constexpr (FWD16) {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -688,120 +657,51 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     if (t == 12345.678f) a.y[0] = (vpt_op16)t;
     return;
   }
-  if constexpr (M16) {
-    if (HAS_RES && (TRACE || CONV_ABLATE == 2 || !VPT_RES_PREFETCH || (VPT_EPI_ABLATE & 4))) XR16(0);
+  if constexpr (FWD16) {
+    if (HAS_RES && (TRACE || CONV_ABLATE == 2)) XR16(0);
   } else {
-    if (HAS_RES && (CONV_ABLATE == 2 || !VPT_RES_PREFETCH)) { LOAD_RES(0); LOAD_RES(1); }
+    if (HAS_RES && CONV_ABLATE == 2) { LOAD_RES(0); LOAD_RES(1); }
   }
   SB();
 
   f32x2 s_sum2 = {0.f, 0.f}, s_sq2 = {0.f, 0.f};   // packed fp32 (v_pk_add_f32 / v_pk_fma_f32): two values per VALU issue
-  // The body is instantiated for NV = 2 and NV = 1 valid 32-channel blocks of this wave (Cout / 32 odd) and selected by one
+  // Both epilogue bodies are instantiated for NV = 2 and NV = 1 valid 32-channel blocks of this wave (Cout / 32 odd) and selected by one
   // uniform branch: with no control flow inside, the waits on the prefetched table / residual pieces stay counted.
+  // ---- dgrad epilogue (32x32 accumulators, lane-swap layout: see "epilogue addressing" above):  dy = acc + c0 + c1 * xin (+ skip connection, mode 3;
+  // gated and scaled for conv0, mode 6) ----
   auto epilogue = [&](auto nv_) __attribute__((always_inline)) {
   constexpr int NV = decltype(nv_)::value;
-  int eoff[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const int y = ty0 + wm * 8 + 2 * m + sub_row(l31);
-    const int x = tx0 + (l31 & 15);
-    const int ey = (y == 0) ? 0 : ((y == a.H - 1) ? 2 : 1);
-    const int ex = (x == 0) ? 0 : ((x == a.W - 1) ? 2 : 1);
-    eoff[m] = (ey * 3 + ex) * 128 + wn * 64 + 4 * hi;
-  }
-  const float* kk = (const float*)(smem + KK_O);
-  constexpr bool use_x = USE_X;
-  u32x4 xq[2][2][2];          // dgrad: the forward layer's input, [parity of m][n2][pair], one subtile ahead
+  const int row_l = sub_row(l31); (void)row_l;   // unused, and it stays: without this evaluation inside the lambda the dgrad kernels' prologue instructions come out in another order
+  u32x4 xq[2][2][2];          // the forward layer's input, [parity of m][n2][pair], one subtile ahead
   u32x4 outv[4][2][2];        // packed results: ALL stores are issued after the last load has been consumed.  gfx950 has one
                               // counter (vmcnt) for loads and stores, which may retire out of order relative to each other, so a
                               // wait for a load issued among stores degenerates to vmcnt(0) = "every store has reached L2" --
                               // the round-2 trace showed the first subtile waiting 4-14 us that way.
-  // Forward: the constant table of the GroupNorm fold, one subtile AHEAD.  Read at the point of use (two ds_read_b128, wait,
-  // eight FMAs) every pair paid a full LDS round trip behind the co-resident workgroup's fragment reads -- 32 exposed round
-  // trips per tile, which is why an epilogue beside a main loop took twice as long as one beside another epilogue and the two
-  // workgroups of a CU re-locked their phases within one tile even when started half a period apart.
-  f32x4 kq[2][4];             // [parity of chunk c = 2 m + n2][channel group g], one chunk (half a subtile, ~150 VALU) ahead
-#define LOAD_KK(c_)                                                                                       \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) kq[(c_) & 1][g_] = *(const f32x4*)(kk + eoff[(c_) >> 1] + ((c_) & 1) * 32 + 8 * g_)
-#define LOAD_XIN(m_)                                                                                      \
-  _Pragma("unroll") for (int n2_ = 0; n2_ < 2; ++n2_)                                                     \
-    _Pragma("unroll") for (int p_ = 0; p_ < 2; ++p_) xq[(m_) & 1][n2_][p_] = EPI_LD(a.xin, m_, n2_, p_)
-  if (use_x) LOAD_XIN(0);
-  if (!BWD) LOAD_KK(0);
+  LOAD_XIN(0);
   SB();
-
-  // 16-byte piece {first half x, y | second half z, w} of a lane pair -> this lane's own 8 bytes of group 2p (e) and 2p + 1 (o)
-#define UNSWAP(v_, e_, o_)                                                                                \
-  do {                                                                                                    \
-    const auto s0_ = __builtin_amdgcn_permlane32_swap((v_).x, (v_).z, false, false);                      \
-    const auto s1_ = __builtin_amdgcn_permlane32_swap((v_).y, (v_).w, false, false);                      \
-    (e_).x = s0_[0]; (o_).x = s0_[1]; (e_).y = s1_[0]; (o_).y = s1_[1];                                   \
-  } while (0)
-  const f32x2 zero2 = {0.f, 0.f};
-  const f32x2 rstd2 = {rstd * RELU_S, rstd * RELU_S}, c0f2 = {c0f, c0f}, c1f2 = {c1f, c1f}, ress2 = {res_s, res_s}, rgate2 = {rgate, rgate};
-  const f32x2 relu_inv2 = {RELU_INV, RELU_INV};
-  // mode 5: the residual's per-channel bias of this lane's channels.  Read per chunk (4 x ds_read_b128 right behind the chunk's table prefetch, ~20
-  // VALU instructions before their first use) instead of held for the whole epilogue: 16 registers instead of 32 -- round 4's version spilled 2 VGPRs.
-  f32x4 bq[4];
-  const float* btab = (const float*)(smem + BT_O) + wn * 64 + 4 * hi;
+  const f32x2 c0f2 = {c0f, c0f}, c1f2 = {c1f, c1f}, rgate2 = {rgate, rgate};
 
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    if (HAS_RES && m < 2 && !(VPT_EPI_ABLATE & 2)) LOAD_RES(m + 2);   // rolling prefetch, two subtiles ahead (0 / 1 were requested during the last channel block)
-    if (use_x && m < 3) LOAD_XIN(m + 1);   // next subtile's xin: in flight while this one is processed
+    if (HAS_RES && m < 2) LOAD_RES(m + 2);   // rolling prefetch, two subtiles ahead (0 / 1 were requested during the last channel block)
+    if (m < 3) LOAD_XIN(m + 1);   // next subtile's xin: in flight while this one is processed
     SB();
 #pragma unroll
     for (int n2 = 0; n2 < 2; ++n2) {
-      if (!BWD && 2 * m + n2 < 7) { LOAD_KK(2 * m + n2 + 1); SB(); }
       if (n2 >= NV) continue;
-      if (RES_AFF) {
-#pragma unroll
-        for (int g_ = 0; g_ < 4; ++g_) bq[g_] = *(const f32x4*)(btab + n2 * 32 + 8 * g_);
-        SB();
-      }
       u32x4 ovp[2], xp[2];
-#if !VPT_RES_NATIVE
-      u32x4 rp[2];
-#endif
-      // residual / xin arrive as whole pixel rows (instruction j: the pixels of lanes (l31 & 15) + 16 j); the same exchange as for
-      // the stores, run backwards, gives every lane the two 16-byte pieces (p = 0, 1) of its own pixel
-#define ROWS_TO_PIECES(src_, dst_)                                                                        \
-  _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_) {                                                      \
-    const auto sw_ = __builtin_amdgcn_permlane16_swap((src_)[0][j_], (src_)[1][j_], false, false);        \
-    (dst_)[0][j_] = sw_[0]; (dst_)[1][j_] = sw_[1];                                                       \
-  }
-#if !VPT_RES_NATIVE
-      if (HAS_RES) ROWS_TO_PIECES(rq[(VPT_EPI_ABLATE & 2) ? (m & 1) : m][n2], rp);
-#endif
-      if (use_x) ROWS_TO_PIECES(xq[m & 1][n2], xp);
-#undef ROWS_TO_PIECES
+      // xin arrives as whole pixel rows: the same exchanges as for the stores, run backwards
+      ROWS_TO_PIECES(xq[m & 1][n2], xp);
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        u32x2 r2[2] = {{0u, 0u}, {0u, 0u}}, x2[2] = {{0u, 0u}, {0u, 0u}}, pk[2];
-#if VPT_RES_NATIVE
-        if (HAS_RES) { r2[0] = rq[(VPT_EPI_ABLATE & 2) ? (m & 1) : m][n2][2 * p]; r2[1] = rq[(VPT_EPI_ABLATE & 2) ? (m & 1) : m][n2][2 * p + 1]; }
-#else
-        if (HAS_RES) UNSWAP(rp[p], r2[0], r2[1]);
-#endif
-        if (use_x) UNSWAP(xp[p], x2[0], x2[1]);
+        u32x2 r2[2] = {{0u, 0u}, {0u, 0u}}, x2[2], pk[2];
+        if (HAS_RES) { r2[0] = rq[m][n2][2 * p]; r2[1] = rq[m][n2][2 * p + 1]; }
+        UNSWAP(xp[p], x2[0], x2[1]);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const int g = 2 * p + q;
           f32x2 v01 = {acc[m][n2][4 * g + 0], acc[m][n2][4 * g + 1]}, v23 = {acc[m][n2][4 * g + 2], acc[m][n2][4 * g + 3]};
-          if (!BWD) {
-            const f32x4 k4 = kq[n2][g];
-            const f32x2 k01 = {k4.x, k4.y}, k23 = {k4.z, k4.w};
-            if (PACKED_RELU) {   // the ReLU follows the 16-bit pack (below): there is no packed fp32 maximum on gfx950, two v_max_f32 per pair were a quarter of this mode's epilogue
-              v01 = rstd2 * v01 + k01;
-              v23 = rstd2 * v23 + k23;
-            } else if (CLAMP_RELU) {   // 2^-40 * ReLU(rstd v + k) through the clamp modifier (see CLAMP_RELU above)
-              v01 = pk_fma_clamp01(rstd2, v01, k01);
-              v23 = pk_fma_clamp01(rstd2, v23, k23);
-            } else {
-              v01 = __builtin_elementwise_max(rstd2 * v01 + k01, zero2);
-              v23 = __builtin_elementwise_max(rstd2 * v23 + k23, zero2);
-            }
-          } else if (use_x) {  // dgrad: + d(mu, rstd)/dx terms of the GroupNorm statistics
+          {  // + d(mu, rstd)/dx terms of the GroupNorm statistics (c0 + c1 * xin)
             const f32x2 x01 = {op16_lo_to_f32(x2[q].x), op16_hi_to_f32(x2[q].x)}, x23 = {op16_lo_to_f32(x2[q].y), op16_hi_to_f32(x2[q].y)};
             if (GATE) {
               v01 = rgate2 * v01 + (c1f2 * x01 + c0f2);     // rstd0 * dy  (c0, c1 carry rstd0 already)
@@ -817,45 +717,11 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
           }
           if (HAS_RES) {
             const f32x2 r01 = {op16_lo_to_f32(r2[q].x), op16_hi_to_f32(r2[q].x)}, r23 = {op16_lo_to_f32(r2[q].y), op16_hi_to_f32(r2[q].y)};
-            if (RES_AFF) {
-              const f32x4 b4 = bq[g];
-              const f32x2 b01 = {b4.x, b4.y}, b23 = {b4.z, b4.w};
-              if (CLAMP_RELU) {
-                v01 = ress2 * r01 + __builtin_elementwise_fma(v01, relu_inv2, b01);
-                v23 = ress2 * r23 + __builtin_elementwise_fma(v23, relu_inv2, b23);
-              } else {
-                v01 = ress2 * r01 + (v01 + b01);
-                v23 = ress2 * r23 + (v23 + b23);
-              }
-            } else if (CLAMP_RELU) {
-              v01 = __builtin_elementwise_fma(v01, relu_inv2, r01);
-              v23 = __builtin_elementwise_fma(v23, relu_inv2, r23);
-            } else {
-              v01 += r01;
-              v23 += r23;
-            }
+            v01 += r01;   // mode 3: the block's skip connection
+            v23 += r23;
           }
           pk[q].x = pack_op16x2(v01.x, v01.y);
           pk[q].y = pack_op16x2(v23.x, v23.y);
-          if (!BWD && !PACKED_RELU) {   // frame statistics of the output (the next layer's GroupNorm), from the stored pairs; dgrad has no consumer for them
-            s_sum2.x = dot2_op16(pk[q].x, OP16_ONE2, s_sum2.x);
-            s_sum2.y = dot2_op16(pk[q].y, OP16_ONE2, s_sum2.y);
-            s_sq2.x = dot2_op16(pk[q].x, pk[q].x, s_sq2.x);
-            s_sq2.y = dot2_op16(pk[q].y, pk[q].y, s_sq2.y);
-          }
-          if (PACKED_RELU) {
-            // Round 5: ReLU as ONE packed signed-16-bit maximum per pair on the rounded bit patterns (positive 16-bit floats
-            // order like integers, negative ones -- and -0 -- are negative integers; rounding is monotone, so max(round(v), 0) == round(max(v, 0)):
-            // bit-identical outputs), and the frame statistics from the packed pair by v_dot2 (products of two 16-bit operands are exact in fp32):
-            // 5 instructions per value pair instead of 6, and the statistics are those of the STORED tensor -- what the next layer's GroupNorm
-            // normalises and what the reference's nn.GroupNorm sees.  Two independent accumulator chains per moment.
-            pk[q].x = relu_op16x2(pk[q].x);
-            pk[q].y = relu_op16x2(pk[q].y);
-            s_sum2.x = dot2_op16(pk[q].x, OP16_ONE2, s_sum2.x);
-            s_sum2.y = dot2_op16(pk[q].y, OP16_ONE2, s_sum2.y);
-            s_sq2.x = dot2_op16(pk[q].x, pk[q].x, s_sq2.x);
-            s_sq2.y = dot2_op16(pk[q].y, pk[q].y, s_sq2.y);
-          }
         }
         // back to 16 contiguous bytes per lane (the swap is an involution) and out
         const auto o0 = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
@@ -880,9 +746,6 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       }
     }
   }
-#undef LOAD_KK
-#undef UNSWAP
-#undef LOAD_XIN
   if (DEFER_STORES)
 #pragma unroll
   for (int m = 0; m < 4; ++m)
@@ -890,35 +753,29 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     for (int n2 = 0; n2 < NV; ++n2) {
 #pragma unroll
       for (int p = 0; p < 2; ++p)
-        if (!(VPT_EPI_ABLATE & 1) || s_sum2.x == 12345.678f) *(u32x4*)((char*)(a.y + cbase[n2]) + (svoff[p] + (unsigned)m * gm_b)) = outv[m][n2][p];
+        *(u32x4*)((char*)(a.y + cbase[n2]) + (svoff[p] + (unsigned)m * gm_b)) = outv[m][n2][p];
     }
   };
-  // ---- M16 epilogue: everything in the accumulators' own layout.  Lane (c16, q16) holds, per pixel row j and 32-cout block n2, the 8 values of couts
-  // 8 q16 .. + 7 of pixel pcol (accumulator elements 8 n2 .. 8 n2 + 7 of ac[j]): two f32x4 of the constant table, ONE 16-byte residual load and
-  // ONE 16-byte store per lane -- whole 128-byte lines, no lane exchange anywhere.  Per value the arithmetic (fold, clamp / packed ReLU, residual
-  // FMA, rounding, v_dot2 statistics) is that of the 32x32 epilogue above.  The edge class of a row differs from "interior" only on the wave's
-  // first row (image top) and last row (image bottom).
+  // ---- forward epilogue: everything in the 16x16 accumulators' own layout.  Lane (c16, q16) holds, per pixel row j and 32-cout block n2, the 8 values
+  // of couts 8 q16 .. + 7 of pixel pcol (accumulator elements 8 n2 .. 8 n2 + 7 of ac[j]): two f32x4 of the constant table, ONE 16-byte residual load
+  // and ONE 16-byte store per lane -- whole 128-byte lines, no lane exchange anywhere.  Per value: GroupNorm fold, ReLU (packed / clamp, see PACKED_RELU
+  // and CLAMP_RELU), residual FMA, rounding, frame statistics of the STORED tensor by v_dot2 (products of two 16-bit operands are exact in fp32) -- what
+  // the next layer's GroupNorm normalises.  The edge class of a row differs from "interior" only on the wave's first row (image top) and last row (bottom).
   // (derived from a copy of the lane id the compiler cannot see through: computed HERE, not held in registers across the main loop)
   int lane_l = lane;
   asm volatile("" : "+v"(lane_l));
   const int c16_l = lane_l & 15, q16_l = lane_l >> 4;
   const int pcol_l = (c16_l < 4) ? 2 * c16_l : ((c16_l < 12) ? 2 * (c16_l - 4) + 1 : 2 * (c16_l - 8));
   const unsigned voff16_l = (unsigned)(((ty0 + wm * 8) * a.W + tx0 + pcol_l) * 32 + 8 * q16_l) * 2u;
-#define XR16L(j_) do { rq16[j_][0] = *(const u32x4*)((const char*)(resp + cbase[0]) + (voff16_l + (unsigned)(j_) * gj_b)); rq16[j_][1] = *(const u32x4*)((const char*)(resp + cbase[1]) + (voff16_l + (unsigned)(j_) * gj_b)); } while (0)
   const int x16_ = tx0 + pcol_l;
   const int ex16 = (x16_ == 0) ? 0 : ((x16_ == a.W - 1) ? 2 : 1);
   const int eo_top = (ty0 + wm * 8 == 0) ? 0 : 3 * 128, eo_bot = (ty0 + wm * 8 + 7 == a.H - 1) ? 6 * 128 : 3 * 128;
   const float* kk16 = (const float*)(smem + KK_O) + ex16 * 128 + wn * 64 + 8 * q16_l;
-#define EO16(j_) ((j_) == 0 ? eo_top : ((j_) == 7 ? eo_bot : 3 * 128))
   auto epilogue16 = [&](auto nv_) __attribute__((always_inline)) {
     constexpr int NV = decltype(nv_)::value;
-    u32x4 outv[8][2];          // packed results: all stores are issued after the last load has been consumed (see the 32x32 epilogue)
-    f32x4 kq[2][2];            // constant table [parity of chunk c = 2 j + n2][half h], one chunk ahead
-#define LOAD_KK16(c_)                                                                                     \
-  do {                                                                                                    \
-    const float* kp_ = kk16 + EO16((c_) >> 1) + ((c_) & 1) * 32;                                          \
-    kq[(c_) & 1][0] = *(const f32x4*)kp_; kq[(c_) & 1][1] = *(const f32x4*)(kp_ + 4);                     \
-  } while (0)
+    u32x4 outv[8][2];          // packed results: all stores are issued after the last load has been consumed (see the dgrad epilogue)
+    f32x4 kq[2][2];            // constant table [parity of chunk c = 2 j + n2][half h], one chunk AHEAD: read at the point of use every chunk paid a full
+                               // LDS round trip behind the co-resident workgroup's fragment reads
     LOAD_KK16(0);
     SB();
     const f32x2 zero2 = {0.f, 0.f};
@@ -978,7 +835,8 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
           }
           pk[h].x = pack_op16x2(v01.x, v01.y);
           pk[h].y = pack_op16x2(v23.x, v23.y);
-          if (PACKED_RELU) {   // ReLU on the rounded bit patterns (bit-identical to an fp32 maximum before the rounding, see the 32x32 epilogue)
+          if (PACKED_RELU) {   // ReLU as ONE packed signed-16-bit maximum per pair on the ROUNDED bit patterns: positive 16-bit floats order like integers,
+                               // negative ones (and -0) are negative integers, rounding is monotone, so max(round(v), 0) == round(max(v, 0)) bit for bit
             pk[h].x = relu_op16x2(pk[h].x);
             pk[h].y = relu_op16x2(pk[h].y);
           }
@@ -990,12 +848,11 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         outv[j][n2] = u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
       }
     }
-#undef LOAD_KK16
 #pragma unroll
     for (int j = 0; j < 8; ++j)
 #pragma unroll
       for (int n2 = 0; n2 < NV; ++n2)
-        if (!(VPT_EPI_ABLATE & 1) || s_sum2.x == 12345.678f) *(u32x4*)((char*)(a.y + cbase[n2]) + (voff16_l + (unsigned)j * gj_b)) = outv[j][n2];
+        *(u32x4*)((char*)(a.y + cbase[n2]) + (voff16_l + (unsigned)j * gj_b)) = outv[j][n2];
   };
   if constexpr (POOL) {
     // The four pointers only this epilogue uses are read from the kernarg segment HERE, through a pointer the compiler cannot see behind: taken from
@@ -1003,8 +860,8 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     // arg-max mode (7) that was the eight registers too many (8 SGPRs spilled to VGPR lanes around the loop).
     const __attribute__((address_space(4))) VptConv3x3Args* late = (const __attribute__((address_space(4))) VptConv3x3Args*)__builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(late));
-    int tid_p = threadIdx.x;   // M16: the thread-indexed addressing of phase 2 is derived HERE, not held across the main loop
-    if constexpr (M16) { asm volatile("" : "+v"(tid_p)); }
+    int tid_p = threadIdx.x;   // the thread-indexed addressing of phase 2 is derived HERE, not held across the main loop
+    asm volatile("" : "+v"(tid_p));
     const int tid = tid_p, lane = tid_p & 63;
     vpt_op16* const seam_r_p = late->seam_r;
     vpt_op16* const seam_c_p = late->seam_c;
@@ -1012,9 +869,9 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     double* const chs_out_p = late->chs_out;
     // ---- phase 1: GroupNorm fold + ReLU, rounded to 16 bits, into the LDS tile [16 x 16 pixels][128 channels] (pixel pitch PT_RS: the
     // 16 extra bytes spread a column of pixels over the banks).  The tile reuses the halo / weight buffers: every wave must be past
-    // its last fragment read first.  A lane holds 4 consecutive channels of one pixel per accumulator group: one ds_write_b64 each.
+    // its last fragment read first.
     __syncthreads();
-    if constexpr (M16) {   // one ds_write_b128 per lane and (pixel row, 32-cout block): couts 8 q16 .. + 7 of pixel (wm 8 + j, pcol)
+    {   // one ds_write_b128 per lane and (pixel row, 32-cout block): couts 8 q16 .. + 7 of pixel (wm 8 + j, pcol)
       const f32x2 zero2 = {0.f, 0.f};
       const f32x2 rstd2 = {rstd, rstd};
 #pragma unroll
@@ -1030,39 +887,6 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
             const f32x4 k4 = *(const f32x4*)(ke + n2 * 32 + 4 * h);
             const f32x2 k01 = {k4.x, k4.y}, k23 = {k4.z, k4.w};
             f32x2 v01 = {ac[j][8 * n2 + 4 * h + 0], ac[j][8 * n2 + 4 * h + 1]}, v23 = {ac[j][8 * n2 + 4 * h + 2], ac[j][8 * n2 + 4 * h + 3]};
-            if (PMASK) {
-              v01 = __builtin_elementwise_max(rstd2 * v01 + k01, zero2);
-              v23 = __builtin_elementwise_max(rstd2 * v23 + k23, zero2);
-            } else {
-              v01 = rstd2 * v01 + k01;
-              v23 = rstd2 * v23 + k23;
-            }
-            pk[h].x = pack_op16x2(v01.x, v01.y);
-            pk[h].y = pack_op16x2(v23.x, v23.y);
-          }
-          *(u32x4*)(dst + n2 * 64) = u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
-        }
-      }
-    } else {
-      const float* kk = (const float*)(smem + KK_O);
-      const f32x2 zero2 = {0.f, 0.f};
-      const f32x2 rstd2 = {rstd, rstd};
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const int py = wm * 8 + 2 * m + sub_row(l31), px = l31 & 15;
-        const int y = ty0 + py, x = tx0 + px;
-        const int ey = (y == 0) ? 0 : ((y == a.H - 1) ? 2 : 1);
-        const int ex = (x == 0) ? 0 : ((x == a.W - 1) ? 2 : 1);
-        const float* ke = kk + (ey * 3 + ex) * 128 + wn * 64 + 4 * hi;
-        unsigned char* dst = smem + (py * 16 + px) * PT_RS + (wn * 64 + 4 * hi) * 2;
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          if (!nvalid[n2]) continue;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const f32x4 k4 = *(const f32x4*)(ke + n2 * 32 + 8 * g);
-            const f32x2 k01 = {k4.x, k4.y}, k23 = {k4.z, k4.w};
-            f32x2 v01 = {acc[m][n2][4 * g + 0], acc[m][n2][4 * g + 1]}, v23 = {acc[m][n2][4 * g + 2], acc[m][n2][4 * g + 3]};
             if (PMASK) {      // (the masks compare post-ReLU values: a window of negatives must read as a window of zeros)
               v01 = __builtin_elementwise_max(rstd2 * v01 + k01, zero2);
               v23 = __builtin_elementwise_max(rstd2 * v23 + k23, zero2);
@@ -1070,9 +894,10 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
               v01 = rstd2 * v01 + k01;
               v23 = rstd2 * v23 + k23;
             }
-            const u32x2 pk = {pack_op16x2(v01.x, v01.y), pack_op16x2(v23.x, v23.y)};
-            *(u32x2*)(dst + (n2 * 32 + 8 * g) * 2) = pk;
+            pk[h].x = pack_op16x2(v01.x, v01.y);
+            pk[h].y = pack_op16x2(v23.x, v23.y);
           }
+          *(u32x4*)(dst + n2 * 64) = u32x4{pk[0].x, pk[0].y, pk[1].x, pk[1].y};
         }
       }
     }
@@ -1197,17 +1022,53 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
         if (ch < a.Cout) atomicAdd(chs_out_p + ((size_t)f * a.Cout + ch) * 2 + (k >> 3), (double)t);
       }
     }
-  } else if constexpr (M16) {
+  } else if constexpr (FWD16) {
     if (nvalid[1]) epilogue16(std::integral_constant<int, 2>{});
     else if (nvalid[0]) epilogue16(std::integral_constant<int, 1>{});
   } else {
-  if (nvalid[1]) epilogue(std::integral_constant<int, 2>{});
-  else if (nvalid[0]) epilogue(std::integral_constant<int, 1>{});
+    static_assert(BWD, "the 32x32 epilogue is written for the dgrad modes only");
+    if (nvalid[1]) epilogue(std::integral_constant<int, 2>{});
+    else if (nvalid[0]) epilogue(std::integral_constant<int, 1>{});
   }
-#undef EO16
-#undef XR16L
-#undef XR16
+  // both loops' macros
+#undef SB
+#undef NOP_
+#undef ISSUE_B
+#undef GLDS
+#undef XA
+#undef WAIT_BARRIER
+  // the dgrad loop's
+#undef WRITE_HALO
+#undef MM
+#undef MMZ
+#undef FA_LD
+#undef FB_LD
+#undef GROUP_
+#undef GROUP
+#undef GROUP_Z
+#undef GROUP_TAIL
+#undef EPI_LD
+#undef EPI_LDN
+#undef LOAD_RES
+#undef XR
+#undef CONV_STEP
+#undef LOAD_XIN
+#undef ROWS_TO_PIECES
+#undef UNSWAP
+  // the forward loop's
+#undef HALO_WR16
+#undef PA
+#undef WB
+#undef M16A
+#undef G16
+#undef G16R
+#undef TAP16
 #undef EPI_LD16
+#undef XR16
+#undef XR16L
+#undef CONV_STEP16
+#undef EO16
+#undef LOAD_KK16
   float s_sum = s_sum2.x + s_sum2.y, s_sq = s_sq2.x + s_sq2.y;
   if (GATE) {      // one fp64 atomic per tile: this tile's share of sum rstd0 dy xin
     float* red = (float*)(smem + KK_O + KK_BYTES);
