@@ -186,7 +186,9 @@ int vpt_frame_affine_forward(const void* x, void* y, const float* gain, const fl
  * lib/xf.py:251-254, lib/action_head.py:164, lib/scaled_mse_head.py:35).  A bf16 [M][lda]; wpk bf16
  * [ceil(N/128)][K/32][128][32]; bias fp32[N] or NULL; res fp32 [M][ldr] or NULL; out_f32 [M][ldc] and/or
  * out_bf16 [M][ldcb].  splitk > 1 (no ReLU/res): out_f32 is a caller-zeroed [splitk][M][ldc] buffer, split s writes its
- * partial product to slice s and the caller sums the slices -- no atomics, so the result is bit-reproducible.
+ * partial product to slice s and the caller sums the slices -- no atomics, so the result is bit-reproducible.  A bias is allowed with splitk > 1: it
+ * is added in SLICE 0 only, by every kernel behind this entry point (MFMA vector and generic epilogues, weight-streaming kernel), so the sum of the
+ * slices carries it exactly once.  A split whose K run is empty writes nothing: that slice keeps the caller's zeros.
  * mask (optional, bf16 [M][ldm]) zeroes outputs where mask <= 0 before the residual add: the ReLU backward of
  * the BC step's dgrad GEMMs.  The same entry point serves forward, dgrad (W^T packed) and wgrad (A = dY^T). */
 int vpt_linear_forward(const void* A, const void* wpk, const float* bias, const float* res,

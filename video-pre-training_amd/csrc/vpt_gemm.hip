@@ -44,6 +44,9 @@ __device__ __forceinline__ void gemm_epilogue_vec(const VptGemmArgs& a, const f3
         if (!(rvalid && col < a.N)) continue;        // (N % 4 == 0: a group of four columns is valid or invalid as a whole)
         f32x4 v = {acc[m][n2][4 * g + 0], acc[m][n2][4 * g + 1], acc[m][n2][4 * g + 2], acc[m][n2][4 * g + 3]};
         if constexpr ((F & GE_SPLIT) != 0) {
+          if constexpr ((F & GE_BIAS) != 0) {        // the bias lands in slice 0, as in the generic epilogue and in vpt_gemv_kernel
+            if (split == 0) v += *(const f32x4*)(a.bias + col);
+          }
           *(f32x4*)(a.out_f32 + ((size_t)split * a.M + row) * a.ldc + col) = v;
           continue;
         }
@@ -595,7 +598,7 @@ extern "C" int vpt_gemm_launch(const VptGemmArgs* a, hipStream_t stream) {
   const long grid = (long)((a->M + 255) >> 8) * ((a->N + 127) >> 7) * a->splitk;
   if (grid > 0x7fffffffL) return -2;
   unsigned f = 0;
-  if (a->atomic_out) f = GE_SPLIT | GE_OUTF;
+  if (a->atomic_out) f = GE_SPLIT | GE_OUTF | (a->bias ? GE_BIAS : 0u);
   else f = (a->bias ? GE_BIAS : 0u) | (a->relu ? GE_RELU : 0u) | (a->mask ? GE_MASK : 0u) | (a->res ? GE_RES : 0u) | (a->out_f32 ? GE_OUTF : 0u) | (a->out_bf16 ? GE_OUTB : 0u);
   const bool aligned = !(a->N & 3) && (!a->out_f32 || !(a->ldc & 3)) && (!a->out_bf16 || !(a->ldcb & 3)) && (!a->res || !(a->ldr & 3)) && (!a->mask || !(a->ldm & 3))
                        && (!a->bias || !((uintptr_t)a->bias & 15)) && (!a->out_f32 || !((uintptr_t)a->out_f32 & 15)) && (!a->res || !((uintptr_t)a->res & 15))
@@ -627,6 +630,7 @@ extern "C" int vpt_gemm_launch(const VptGemmArgs* a, hipStream_t stream) {
       case GE_RES | GE_OUTF: GE_LAUNCH(GE_VEC | GE_RES | GE_OUTF); break;
       case GE_MASK | GE_OUTB: GE_LAUNCH(GE_VEC | GE_MASK | GE_OUTB); break;
       case GE_SPLIT | GE_OUTF: GE_LAUNCH(GE_VEC | GE_SPLIT | GE_OUTF); break;
+      case GE_SPLIT | GE_BIAS | GE_OUTF: GE_LAUNCH(GE_VEC | GE_SPLIT | GE_BIAS | GE_OUTF); break;
       default: done = false;
     }
   }
