@@ -109,6 +109,17 @@ int vpt_conv_first_forward(const uint8_t* img, const void* wfrag, void* y, doubl
 int vpt_conv3d_t5_forward(const uint8_t* img, const void* wfrag, const float* bias, void* y, double* stats_out,
                           int frames, int T, int H, int W, int Cout, void* stream);
 
+/* The same temporal conv with every output frame ("slot") addressed through an index: slot j is centred on img[src[j]], and tap
+ * dt = 0..4 reads img[src[j] + dt - 2] iff lo[j] <= src[j] + dt - 2 < hi[j], zeros otherwise -- the zero padding of
+ * InverseActionNet._conv3d_forward (lib/policy.py:394-403, padding (2,0,0)) at the edges of whichever window [lo, hi) of a longer
+ * video the slot stands for, without copying that window's pixels (run_inverse_dynamics_model.py:146-163 and
+ * inverse_dynamics_model.py:74-95 copy and run one window at a time).  One arithmetic with vpt_conv3d_t5_forward: a slot with
+ * src = f, [lo, hi) = the sequence of frame f gets the bits that entry point gives frame f.
+ * img: uint8 [img_frames][H][W][3]; src, lo, hi: int32 [slots] ([lo, hi) is clipped to [0, img_frames)); y: blocked
+ * [slots][Cout/32][H][W][32]; stats_out (optional, [slots][2]) receives the statistics of y. */
+int vpt_conv3d_t5_forward_indexed(const uint8_t* img, const int32_t* src, const int32_t* lo, const int32_t* hi, const void* wfrag, const float* bias,
+                                  void* y, double* stats_out, int slots, int img_frames, int H, int W, int Cout, void* stream);
+
 /* GroupNorm(1,Cin) -> Conv2d(3x3, pad 1, no bias) -> ReLU [-> + residual].
  * Replaces FanInInitReLULayer.forward (lib/util.py:75-82) for conv layers and the residual add of
  * CnnBasicBlock.forward (lib/impala_cnn.py:50-52).  x, res, y blocked bf16; wpk bf16 [NT][Cin/32][9][128][32];
@@ -489,6 +500,26 @@ int vpt_camera_undiscretize(const long* bins, double* xy, long n, double maxval,
  * outside the grid). */
 int vpt_action_from_factored(const long* buttons, const long* camera, long* joint_buttons, long* joint_camera, long n, int n_camera_bins, void* stream);
 int vpt_action_to_factored(const long* joint_buttons, const long* joint_camera, long* buttons, long* camera, long n, int n_camera_bins, void* stream);
+
+/* ---- IDM video labelling on the device ---- */
+
+/* y[i][:] = x[index[i]][:]: fp32 rows of D values, D % 4 == 0, x and y 16-byte aligned; x [rows_in][D], index int32 [n], y [n][D].
+ * An index outside [0, rows_in) gives a row of zeros.  The windows of a video as lists of feature rows: replaces the host-side
+ * windowing of the pixels in run_inverse_dynamics_model.py:146-163 (one agent.predict_actions(frames) per batch of frames). */
+int vpt_gather_rows(const float* x, const int32_t* index, float* y, long rows_in, long n, int D, void* stream);
+
+/* IDM log-probs -> labels, one launch over n frames.  Replaces InverseActionPolicy.predict's deterministic sample and log-prob
+ * (lib/policy.py:448-464 over lib/action_head.py:176-207) and IDMAgent._agent_action_to_env (inverse_dynamics_model.py:61-72:
+ * `.cpu().numpy()`, then the host's action mapping).  lp_buttons fp32 [n][20][2], lp_camera fp32 [n][2][n_camera_bins] ->
+ *   buttons int64 [n][20], camera int64 [n][2]: arg-max per group, the lowest index on ties (torch.argmax);
+ *   log_prob fp32 [n]: the 22 chosen log-probs added left to right in fp32, buttons first;
+ *   joint_buttons, joint_camera int64 [n]: vpt_action_from_factored of (buttons, camera) (lib/action_mapping.py:179-207);
+ *   camera_deg fp64 [n][2]: vpt_camera_undiscretize of camera (lib/actions.py:100-108) with (maxval, binsize, mu, mu_law);
+ *   null_flag uint8 [n]: 1 iff no button is pressed and both camera bins are the centre bin n_camera_bins / 2 -- the frames the
+ *   reference's loader drops (data_loader.py:48-128). */
+int vpt_idm_decode(const float* lp_buttons, const float* lp_camera, int64_t* buttons, int64_t* camera, float* log_prob, int64_t* joint_buttons,
+                   int64_t* joint_camera, double* camera_deg, uint8_t* null_flag, long n, int n_camera_bins, double maxval, double binsize, double mu,
+                   int mu_law, void* stream);
 
 /* ---- clip data path on the device ---- */
 

@@ -17,21 +17,7 @@
 // drop, inventory, hotbar.1 .. hotbar.9.
 #include "vpt_common.h"
 #include "vpt_kernels.h"
-
-#define B_ATTACK 0
-#define B_BACK 1
-#define B_FORWARD 2
-#define B_JUMP 3
-#define B_LEFT 4
-#define B_RIGHT 5
-#define B_SNEAK 6
-#define B_SPRINT 7
-#define B_USE 8
-#define B_DROP 9
-#define B_INVENTORY 10
-#define B_HOTBAR1 11
-#define N_BUTTONS 20
-#define JOINT_INVENTORY 8640
+#include "vpt_action_codec.h"   // the per-row functions (shared with vpt_labeler.hip) and the button indices
 
 __global__ __launch_bounds__(256) void vpt_camera_discretize_kernel(const double* __restrict__ xy, long* __restrict__ out, long n,
                                                                     double maxval, double binsize, double mu, int mu_law) {
@@ -51,14 +37,7 @@ __global__ __launch_bounds__(256) void vpt_camera_undiscretize_kernel(const long
                                                                       double maxval, double binsize, double mu, int mu_law) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  double v = (double)pq[i] * binsize - maxval;
-  if (mu_law) {
-    v = v / maxval;
-    const double s = (v > 0.0) ? 1.0 : ((v < 0.0) ? -1.0 : 0.0);
-    v = s * (1.0 / mu) * (pow(1.0 + mu, fabs(v)) - 1.0);
-    v *= maxval;
-  }
-  out[i] = v;
+  out[i] = vpt_camera_undiscretize_one(pq[i], maxval, binsize, mu, mu_law);
 }
 
 __global__ __launch_bounds__(256) void vpt_action_from_factored_kernel(const long* __restrict__ buttons, const long* __restrict__ camera,
@@ -66,35 +45,7 @@ __global__ __launch_bounds__(256) void vpt_action_from_factored_kernel(const lon
                                                                        long n, int n_camera_bins) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const long* b = buttons + i * N_BUTTONS;
-  const int null_bin = n_camera_bins / 2;
-  int hotbar = 0;
-#pragma unroll
-  for (int k = 1; k <= 9; ++k)
-    if (b[B_HOTBAR1 + k - 1] != 0) hotbar = k;                       // later button wins
-  const bool fwd = b[B_FORWARD] != 0, back = b[B_BACK] != 0;
-  const int fore_back = (fwd && back) ? 0 : (back ? 2 : (fwd ? 1 : 0)); // both pressed cancel
-  const bool left = b[B_LEFT] != 0, right = b[B_RIGHT] != 0;
-  const int left_right = (left && right) ? 0 : (right ? 2 : (left ? 1 : 0));
-  const int sprint_sneak = (b[B_SNEAK] != 0) ? 2 : ((b[B_SPRINT] != 0) ? 1 : 0);   // sneak is later in the group
-  const long c0 = camera[2 * i], c1 = camera[2 * i + 1];
-  const int camera_on = !(c0 == null_bin && c1 == null_bin);
-  long jb = hotbar;
-  jb = jb * 3 + fore_back;
-  jb = jb * 3 + left_right;
-  jb = jb * 3 + sprint_sneak;
-  jb = jb * 2 + (b[B_USE] != 0);
-  jb = jb * 2 + (b[B_DROP] != 0);
-  jb = jb * 2 + (b[B_ATTACK] != 0);
-  jb = jb * 2 + (b[B_JUMP] != 0);
-  jb = jb * 2 + camera_on;
-  long jc = c0 * n_camera_bins + c1;
-  if (b[B_INVENTORY] == 1) {                                           // exclusive with everything, camera included
-    jb = JOINT_INVENTORY;
-    jc = (long)null_bin * n_camera_bins + null_bin;
-  }
-  joint_buttons[i] = jb;
-  joint_camera[i] = jc;
+  vpt_action_from_factored_one(buttons + i * N_BUTTONS, camera[2 * i], camera[2 * i + 1], n_camera_bins, joint_buttons + i, joint_camera + i);
 }
 
 __global__ __launch_bounds__(256) void vpt_action_to_factored_kernel(const long* __restrict__ joint_buttons, const long* __restrict__ joint_camera,

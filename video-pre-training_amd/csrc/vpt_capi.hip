@@ -102,6 +102,16 @@ int vpt_conv3d_t5_forward(const uint8_t* img, const void* wfrag, const float* bi
   CHECK_LAUNCH(vpt_conv3d_launch(&a, (hipStream_t)stream), "vpt_conv3d_t5_forward");
 }
 
+int vpt_conv3d_t5_forward_indexed(const uint8_t* img, const int32_t* src, const int32_t* lo, const int32_t* hi, const void* wfrag, const float* bias,
+                                  void* y, double* stats_out, int slots, int img_frames, int H, int W, int Cout, void* stream) {
+  if (!img || !src || !lo || !hi || !wfrag || !bias || !y) return fail(-1, "vpt_conv3d_t5_forward_indexed: null pointer");
+  VptConv3dArgs a = {};
+  a.img = img; a.wfrag = (const vpt_op16*)wfrag; a.bias = bias; a.y = (vpt_op16*)y; a.stats_out = stats_out;
+  a.frames = slots; a.T = 1; a.H = H; a.W = W; a.Cout = Cout; a.NT = (Cout + 127) / 128;
+  a.src = src; a.lo = lo; a.hi = hi; a.n_img = img_frames;
+  CHECK_LAUNCH(vpt_conv3d_indexed_launch(&a, (hipStream_t)stream), "vpt_conv3d_t5_forward_indexed");
+}
+
 int vpt_conv3x3_forward(const void* x, const void* wpk, const float* edge_sa, const float* edge_sg,
                         const double* stats_in, const void* res, void* y, double* stats_out,
                         int frames, int H, int W, int Cin, int Cout, void* stream) {
@@ -616,6 +626,19 @@ int vpt_action_from_factored(const long* buttons, const long* camera, long* join
 
 int vpt_action_to_factored(const long* joint_buttons, const long* joint_camera, long* buttons, long* camera, long n, int n_camera_bins, void* stream) {
   CHECK_LAUNCH(vpt_action_mapping_launch(1, joint_buttons, joint_camera, buttons, camera, n, n_camera_bins, (hipStream_t)stream), "vpt_action_to_factored");
+}
+
+/* ---- IDM video labelling (inverse_dynamics_model.py:61-95, run_inverse_dynamics_model.py:146-163) ---- */
+int vpt_gather_rows(const float* x, const int32_t* index, float* y, long rows_in, long n, int D, void* stream) {
+  if (D <= 0 || (D & 3)) return fail(-1, "vpt_gather_rows: D must be a positive multiple of 4");
+  CHECK_LAUNCH(vpt_gather_rows_launch(x, index, y, rows_in, n, D, (hipStream_t)stream), "vpt_gather_rows");
+}
+
+int vpt_idm_decode(const float* lp_buttons, const float* lp_camera, int64_t* buttons, int64_t* camera, float* log_prob, int64_t* joint_buttons,
+                   int64_t* joint_camera, double* camera_deg, uint8_t* null_flag, long n, int n_camera_bins, double maxval, double binsize, double mu,
+                   int mu_law, void* stream) {
+  CHECK_LAUNCH(vpt_idm_decode_launch(lp_buttons, lp_camera, buttons, camera, log_prob, joint_buttons, joint_camera, camera_deg, null_flag, n, n_camera_bins,
+                                     maxval, binsize, mu, mu_law, (hipStream_t)stream), "vpt_idm_decode");
 }
 
 /* ---- clip data path (data_loader.py:34-46,113-122; agent.py:100-103) ---- */

@@ -14,7 +14,11 @@
 #include "vpt_common.h"
 #include "vpt_kernels.h"
 
-__global__ __launch_bounds__(256, 2) void vpt_conv3d_t5_kernel(VptConv3dArgs a) {
+// INDEXED (vpt_conv3d_t5_forward_indexed, the video labeller's shared-feature path): output frame j ("slot") is centred on img[src[j]] and
+// tap dt reads img[src[j] + dt - 2] iff lo[j] <= src[j] + dt - 2 < hi[j] -- the zero padding of whichever window the slot stands for, without
+// a copy of that window's pixels.  The plain kernel is the case src[j] = j, [lo, hi) = the frame's own sequence; both run this one body.
+template <bool INDEXED>
+__device__ __forceinline__ void vpt_conv3d_t5_body(const VptConv3dArgs& a) {
   __shared__ __attribute__((aligned(16))) unsigned char in[5 * 768];
   __shared__ __attribute__((aligned(16))) float bias_s[128];
   __shared__ float red[8];
@@ -25,15 +29,24 @@ __global__ __launch_bounds__(256, 2) void vpt_conv3d_t5_kernel(VptConv3dArgs a) 
   int L = blockIdx.x;
   const int nt = L % a.NT; L /= a.NT;
   const int chunk = L % chunks;
-  const int f = L / chunks;       // frame index b*T + t
-  const int t = f % a.T;
+  const int f = L / chunks;       // output frame: b*T + t, or the slot
   const int p0 = chunk * 256;
+  int fc, f_lo, f_hi;             // centre frame in img and the range of img frames its taps may read
+  if constexpr (INDEXED) {
+    fc = a.src[f];
+    f_lo = max(a.lo[f], 0);       // (never outside img, whatever the plan says)
+    f_hi = min(a.hi[f], a.n_img);
+  } else {
+    fc = f;
+    f_lo = f - f % a.T;
+    f_hi = f_lo + a.T;
+  }
 
   if (tid < 240) {
     const int dt = tid / 48, c16 = tid - dt * 48;  // 48 x 16 B = 768 B per frame slab
-    const int tt = t + dt - 2;
+    const int ft = fc + dt - 2;
     u32x4 v = {0u, 0u, 0u, 0u};
-    if (tt >= 0 && tt < a.T) v = *(const u32x4*)(a.img + ((size_t)(f + dt - 2) * HW + p0) * 3 + c16 * 16);
+    if (ft >= f_lo && ft < f_hi) v = *(const u32x4*)(a.img + ((size_t)ft * HW + p0) * 3 + c16 * 16);
     *(u32x4*)(in + dt * 768 + c16 * 16) = v;
   }
   if (tid < 128) bias_s[tid] = a.bias[nt * 128 + tid];
@@ -92,10 +105,22 @@ __global__ __launch_bounds__(256, 2) void vpt_conv3d_t5_kernel(VptConv3dArgs a) 
   }
 }
 
+__global__ __launch_bounds__(256, 2) void vpt_conv3d_t5_kernel(VptConv3dArgs a) { vpt_conv3d_t5_body<false>(a); }
+__global__ __launch_bounds__(256, 2) void vpt_conv3d_t5_indexed_kernel(VptConv3dArgs a) { vpt_conv3d_t5_body<true>(a); }
+
 extern "C" int vpt_conv3d_launch(const VptConv3dArgs* a, hipStream_t stream) {
   if (((a->H * a->W) & 255) || (a->Cout & 31) || a->frames <= 0 || a->T <= 0 || (a->frames % a->T)) return -1;
   const long grid = (long)a->frames * ((a->H * a->W) >> 8) * a->NT;
   if (grid > 0x7fffffffL) return -2;
   hipLaunchKernelGGL(vpt_conv3d_t5_kernel, dim3((unsigned)grid), dim3(256), 0, stream, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// a->frames = number of slots (frames of y / stats_out), a->n_img = frames of img; a->T is not used
+extern "C" int vpt_conv3d_indexed_launch(const VptConv3dArgs* a, hipStream_t stream) {
+  if (((a->H * a->W) & 255) || (a->Cout & 31) || a->frames <= 0 || a->n_img <= 0 || !a->src || !a->lo || !a->hi) return -1;
+  const long grid = (long)a->frames * ((a->H * a->W) >> 8) * a->NT;
+  if (grid > 0x7fffffffL) return -2;
+  hipLaunchKernelGGL(vpt_conv3d_t5_indexed_kernel, dim3((unsigned)grid), dim3(256), 0, stream, *a);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -112,6 +112,11 @@ struct VptConv3dArgs {
   vpt_op16* y;             // [B*T][Cout/32][H][W][32]
   double* stats_out;       // [B*T][2]
   int frames, T, H, W, Cout, NT;
+  // indexed variant only (vpt_conv3d_indexed_launch): y / stats_out hold `frames` slots, img holds n_img frames
+  const int* src;          // [frames] centre frame of each slot
+  const int* lo;           // [frames] taps read img frames in [lo, hi) only, zeros elsewhere
+  const int* hi;
+  int n_img;
 };
 
 struct VptPoolArgs {
@@ -447,6 +452,11 @@ int vpt_channel_stats_launch(const VptChannelStatsArgs* a, hipStream_t s);
 int vpt_nfold_coef_launch(const VptNfoldCoefArgs* a, hipStream_t s);
 int vpt_conv_first_launch(const VptConvFirstArgs* a, hipStream_t s);
 int vpt_conv3d_launch(const VptConv3dArgs* a, hipStream_t s);
+int vpt_conv3d_indexed_launch(const VptConv3dArgs* a, hipStream_t s);
+int vpt_gather_rows_launch(const float* x, const int32_t* index, float* y, long rows_in, long n, int D, hipStream_t s);
+int vpt_idm_decode_launch(const float* lp_buttons, const float* lp_camera, int64_t* buttons, int64_t* camera, float* log_prob, int64_t* joint_buttons,
+                          int64_t* joint_camera, double* camera_deg, uint8_t* null_flag, long n, int n_camera_bins, double maxval, double binsize, double mu,
+                          int mu_law, hipStream_t s);
 int vpt_pool_launch(const VptPoolArgs* a, hipStream_t s);
 int vpt_affine_launch(const VptAffineArgs* a, hipStream_t s);
 int vpt_gemm_launch(const VptGemmArgs* a, hipStream_t s);

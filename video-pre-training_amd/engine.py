@@ -744,3 +744,70 @@ class IDMEngine(PolicyEngine):
             rng[1:].add_(1)
         out["latent"] = latent.view(bsz, t, hid)
         return out
+
+    @torch.no_grad()
+    def forward_windows(self, frames_u8: torch.Tensor, window: int, stride: int, share_features: bool = True, windows_per_call: int = 8):
+        """Label a whole video: frames_u8 uint8 [N,128,128,3] in overlapping windows (packing.label_windows), every frame taking the log-probs of
+        the window in which it is most central -> ops.idm_decode's dict of labels plus pd = {"buttons": fp32 [N,20,2], "camera": fp32 [N,2,n_bins]}
+        (the stitched log-probs) and plan (packing.IDMFeaturePlan).
+
+        share_features=True computes the per-frame part of the net -- temporal conv, IMPALA CNN, dense, 256 -> hid linear: ~99 % of the FLOPs --
+        once per distinct (frame, clipped temporal neighbourhood) instead of once per window row (packing.idm_feature_plan: N + 4 W slots at most
+        against W L rows; the temporal conv reads the video in place through an index, ops.conv3d_t5_indexed), gathers the slots into window
+        rows for the transformer blocks, `windows_per_call` windows per launch, and gathers the N labelling rows in front of final_ln and the
+        heads, which so run once per frame.  share_features=False runs forward() on copies of the windows' pixels and selects the same rows:
+        the window-by-window baseline.  Both decode with one ops.idm_decode launch."""
+        if not self.packed:
+            raise RuntimeError("IDMEngine.pack(state_dict) must be called before forward_windows")
+        if frames_u8.dim() != 4 or tuple(frames_u8.shape[1:]) != (128, 128, 3) or frames_u8.dtype != torch.uint8:
+            raise ValueError(f"forward_windows: frames must be uint8 [N,128,128,3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+        if int(windows_per_call) < 1:
+            raise ValueError("windows_per_call must be at least 1")
+        cfg, w = self.cfg, self.w
+        frames = frames_u8.contiguous()
+        dev = frames.device
+        n = frames.shape[0]
+        plan = packing.idm_feature_plan(n, window, stride)
+        n_win, t = plan.starts.numel(), plan.length
+        hid, heads = cfg["hidsize"], cfg["heads"]
+        sk = self.linear_splitk
+        per_call = int(windows_per_call)
+        if not share_features:
+            rows = (plan.starts.to(torch.int64).view(n_win, 1) + torch.arange(t).view(1, t)).to(dev)
+            lps = {"buttons": [], "camera": []}
+            for k in range(0, n_win, per_call):
+                out = self.forward(frames[rows[k:k + per_call].reshape(-1)].view(-1, t, 128, 128, 3))
+                for h in lps:
+                    lps[h].append(out[h].reshape(-1, *out[h].shape[2:]))
+            sel = plan.sel_rows.to(dev, torch.int64)
+            lp = {h: torch.cat(v, 0).index_select(0, sel).contiguous() for h, v in lps.items()}
+        else:
+            src, lo, hi = plan.src.to(dev), plan.lo.to(dev), plan.hi.to(dev)
+            wfrag, bias = w["conv3d"]
+            outs = []
+            for i in range(0, src.numel(), self.cnn_chunk):
+                j = min(i + self.cnn_chunk, src.numel())
+                s0 = torch.zeros(j - i, 2, dtype=torch.float64, device=dev)
+                x0 = ops.conv3d_t5_indexed(frames, src[i:j], lo[i:j], hi[i:j], wfrag, bias, self.c3d_out, stats_out=s0)
+                outs.append(self._cnn_dense(None, x0=x0, s_x0=s0))
+                del x0
+            x = self._img_linear(outs[0] if len(outs) == 1 else torch.cat(outs, 0), splitk=sk)
+            if cfg["use_pre_lstm_ln"]:
+                x, _ = ops.layernorm(x, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=self.dtype)
+            xw = ops.gather_rows(x, plan.win_rows.to(dev))                      # [W t, hid]: every window's rows, in window order
+            del x
+            for k in range(0, n_win, per_call):
+                nb = min(per_call, n_win - k)
+                xc = xw[k * t:(k + nb) * t]
+                for l in range(cfg["n_layers"]):
+                    xc = self._block(xc, l, "throughput", sk, lambda qkv: ops.full_attention(qkv, nb, t, heads, hid, dtype=self.dtype))
+                xw[k * t:(k + nb) * t] = xc
+            xs = ops.gather_rows(xw, plan.sel_rows.to(dev))                      # [N, hid]: the row that labels each frame
+            _, lb = ops.layernorm(xs, w["final.g"], w["final.b"], relu_in=True, out_f32=True, dtype=self.dtype)     # (as forward() calls it)
+            lp = {}
+            for h, (n_groups, nc) in (("buttons", self.button_shape), ("camera", self.camera_shape)):
+                z, _ = ops.linear(lb, w[h + ".w"], n_groups * nc, bias=w[h + ".b"], tiling="throughput", splitk=sk)
+                lp[h] = action_heads(z, ((h, 0, n_groups, nc),), 1, n, cfg["temperature"])[h].view(n, n_groups, nc)
+        out = ops.idm_decode(lp["buttons"], lp["camera"])
+        out.update(pd=lp, plan=plan)
+        return out

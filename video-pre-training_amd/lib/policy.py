@@ -643,6 +643,7 @@ class InverseActionPolicy(nn.Module):
         pi_head_kwargs = {} if pi_head_kwargs is None else pi_head_kwargs
         self.pi_head = make_action_head(self.action_space, self.net.output_latent_size(), **pi_head_kwargs)
         self._cfg = config_from_policy_kwargs(idm_net_kwargs, pi_head_kwargs)
+        self._timesteps = idm_net_kwargs.get("timesteps")        # label_video's default window
         bt, ct = action_space["buttons"], action_space["camera"]
         self._engine = IDMEngine(self._cfg, (bt.size, bt.eltype.n), (ct.size, ct.eltype.n), precision=precision)
         self._packed_key = None
@@ -705,3 +706,19 @@ class InverseActionPolicy(nn.Module):
         log_prob = extra["action_log_prob"]
         assert not torch.isnan(log_prob).any()
         return ac, state_out, {"log_prob": log_prob, "pd": pd}
+
+    @torch.no_grad()
+    def label_video(self, frames, window: Optional[int] = None, stride: Optional[int] = None, share_features: bool = True, windows_per_call: int = 8):
+        """Pseudo-label a whole recording: frames uint8 [N,128,128,3] on the model's device -> labeler.VideoLabels (deterministic labels, their
+        log-probs, the policy's joint indices for BC, camera angles, the null flag; everything stays on the device).  The video is read in
+        windows of `window` frames (default: the model's `timesteps`) every `stride` frames (default window // 2), and each frame takes the
+        prediction of the window in which it is most central (packing.label_windows) -- what running `predict` on every window and stitching
+        the answers gives, without copying windows of pixels or running the per-frame part of the net twice on frames two windows share
+        (IDMEngine.forward_windows; share_features=False is that window-by-window path).  Frames of another size are the caller's job:
+        ops.clip_frames resizes decoded video frames to 128x128 on the device."""
+        from ..labeler import VideoLabels
+        self._ensure_packed()
+        window = int(window if window is not None else (self._timesteps or 128))
+        stride = int(stride if stride is not None else max(1, window // 2))
+        out = self._engine.forward_windows(frames, window, stride, share_features=share_features, windows_per_call=windows_per_call)
+        return VideoLabels(**{k: out[k] for k in ("buttons", "camera", "log_prob", "joint_buttons", "joint_camera", "camera_deg", "null", "pd", "plan")})

@@ -503,6 +503,66 @@ def conv3d_t5(img_u8, wfrag, bias, cout, t, stats_out=None):
     return y
 
 
+def conv3d_t5_indexed(img_u8, src, lo, hi, wfrag, bias, cout, stats_out=None):
+    """The temporal conv with indexed output frames: img_u8 [F, H, W, 3] uint8, src / lo / hi int32 [S] -> blocked [S, cout/32, H, W, 32].
+    Slot j is centred on img_u8[src[j]]; tap dt reads img_u8[src[j] + dt - 2] iff lo[j] <= src[j] + dt - 2 < hi[j], zeros otherwise
+    (packing.idm_feature_plan: a window's zero padding without a copy of its pixels)."""
+    _chk(img_u8, torch.uint8, "img"); _chk(wfrag, OP16, "wfrag"); _chk(bias, torch.float32, "bias")
+    _chk(stats_out, torch.float64, "stats_out")
+    for name, t in (("src", src), ("lo", lo), ("hi", hi)):
+        _chk(t, torch.int32, name)
+        if t.dim() != 1 or t.numel() != src.numel():
+            raise ValueError(f"conv3d_t5_indexed: {name} must be int32 [{src.numel()}], got {tuple(t.shape)}")
+    f, h, w, _ = img_u8.shape
+    s = src.numel()
+    if stats_out is not None and stats_out.numel() != 2 * s:
+        raise ValueError(f"conv3d_t5_indexed: stats_out must hold [{s}, 2] values, got {tuple(stats_out.shape)}")
+    dt, fmt = _fmt(wfrag)
+    y = torch.empty(s, cout // 32, h, w, 32, dtype=dt, device=img_u8.device)
+    if s:
+        _call("vpt_conv3d_t5_forward_indexed", dict(flops=2.0 * s * h * w * cout * 15, bytes=s * h * w * (15 + 2 * cout)),
+              ptr(img_u8), ptr(src), ptr(lo), ptr(hi), ptr(wfrag), ptr(bias), ptr(y), ptr(stats_out), s, f, h, w, cout, _stream(), fmt=fmt)
+    return y
+
+
+def gather_rows(x, index, out=None):
+    """y[i] = x[index[i]]: x fp32 [R, D] (D % 4 == 0), index int32 [n] -> fp32 [n, D]; an index outside [0, R) gives a row of zeros."""
+    _chk(x, torch.float32, "x"); _chk(index, torch.int32, "index"); _chk(out, torch.float32, "out")
+    if x.dim() != 2 or index.dim() != 1:
+        raise ValueError("gather_rows: x must be [R, D] and index [n]")
+    r, d = x.shape
+    n = index.numel()
+    if d % 4 or r == 0:
+        raise ValueError(f"gather_rows: needs D % 4 == 0 and at least one input row, got x {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(n, d, dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (n, d) or out.device != x.device:
+        raise ValueError(f"gather_rows: out must be fp32 [{n}, {d}] on {x.device}")
+    if n:
+        _call("vpt_gather_rows", dict(bytes=8.0 * n * d), ptr(x), ptr(index), ptr(out), r, n, d, _stream())
+    return out
+
+
+def idm_decode(lp_buttons, lp_camera, maxval=10, binsize=2, mu=10, mu_law=True):
+    """IDM log-probs (buttons fp32 [N, 20, 2], camera fp32 [N, 2, n_bins]) -> dict of labels, one launch: buttons int64 [N, 20], camera int64
+    [N, 2] (arg-max, lowest index on ties), log_prob fp32 [N] (the 22 chosen log-probs added left to right), joint_buttons / joint_camera
+    int64 [N] (action_from_factored of them), camera_deg fp64 [N, 2] (camera_undiscretize), null uint8 [N] (nothing pressed, camera centred)."""
+    _chk(lp_buttons, torch.float32, "lp_buttons"); _chk(lp_camera, torch.float32, "lp_camera")
+    n = lp_buttons.shape[0]
+    if tuple(lp_buttons.shape) != (n, 20, 2) or lp_camera.dim() != 3 or tuple(lp_camera.shape[:2]) != (n, 2) or not lp_camera.shape[2] & 1:
+        raise ValueError(f"idm_decode: expected log-probs [N, 20, 2] and [N, 2, odd n_bins], got {tuple(lp_buttons.shape)} and {tuple(lp_camera.shape)}")
+    dev = lp_buttons.device
+    out = dict(buttons=torch.empty(n, 20, dtype=torch.int64, device=dev), camera=torch.empty(n, 2, dtype=torch.int64, device=dev),
+               log_prob=torch.empty(n, dtype=torch.float32, device=dev), joint_buttons=torch.empty(n, dtype=torch.int64, device=dev),
+               joint_camera=torch.empty(n, dtype=torch.int64, device=dev), camera_deg=torch.empty(n, 2, dtype=torch.float64, device=dev),
+               null=torch.empty(n, dtype=torch.uint8, device=dev))
+    if n:
+        _call("vpt_idm_decode", dict(bytes=float(n) * (160 + 8 * lp_camera.shape[2] + 250)), ptr(lp_buttons), ptr(lp_camera), ptr(out["buttons"]),
+              ptr(out["camera"]), ptr(out["log_prob"]), ptr(out["joint_buttons"]), ptr(out["joint_camera"]), ptr(out["camera_deg"]), ptr(out["null"]),
+              n, int(lp_camera.shape[2]), float(maxval), float(binsize), float(mu), int(bool(mu_law)), _stream())
+    return out
+
+
 def full_attention(qkv, batch, t, heads, hid, dtype=torch.bfloat16):
     """Mask "none", no memory (IDM): every query attends to all t rows of its chunk.  qkv [B*t, 3*hid] fp32."""
     _chk(qkv, torch.float32, "qkv")

@@ -3,6 +3,7 @@
 All functions take fp32 torch tensors with the reference's shapes (the `.weights` state_dict,
 SURVEY.md §8b) and return new tensors on the same device; the fp32 masters are left untouched.
 """
+import collections
 import math
 
 import torch
@@ -169,6 +170,68 @@ def episode_bounds(first, state_mask, maxlen):
     rows = torch.cat([state_mask, torch.ones(bsz, t, dtype=torch.bool, device=dev)], dim=1)   # validity of every row of [memory ; chunk]
     j = t + torch.arange(maxlen, device=dev).view(1, maxlen)
     return qlo, rows[:, t:] & (j >= qlo[:, -1:])
+
+
+MAX_LABEL_WINDOW = 160     # the mask="none" attention kernel's longest chunk (IDMEngine.forward)
+
+LabelWindows = collections.namedtuple("LabelWindows", "starts length owner")
+IDMFeaturePlan = collections.namedtuple("IDMFeaturePlan", "n_frames window stride starts length owner src lo hi win_rows sel_rows")
+
+
+def label_windows(n_frames: int, window: int, stride: int) -> LabelWindows:
+    """The overlapping windows a video of n_frames is labelled in, and the window each frame takes its label from (host integers).
+    Windows start at 0, stride, 2 stride, ... while start + window <= n_frames, plus one at n_frames - window if the last of those does
+    not end the video; a video shorter than `window` is one window of its own length.  Frame f belongs to the window in which it is most
+    central -- the smallest |2 (f - start) - (length - 1)|, the earlier window on ties -- so at window 128, stride 64 an interior window
+    labels its offsets 32..95, and only the first and the last window label frames near their own edges.
+    -> (starts int32 [W], length, owner int32 [n_frames])."""
+    n, L, S = int(n_frames), int(window), int(stride)
+    if n < 1:
+        raise ValueError("label_windows: n_frames must be at least 1")
+    if not (1 <= S <= L <= MAX_LABEL_WINDOW):
+        raise ValueError(f"label_windows: need 1 <= stride <= window <= {MAX_LABEL_WINDOW}, got window {L}, stride {S}")
+    if n < L:
+        starts, L = [0], n
+    else:
+        starts = list(range(0, n - L + 1, S))
+        if starts[-1] != n - L:
+            starts.append(n - L)
+    st = torch.tensor(starts, dtype=torch.int64)
+    f = torch.arange(n, dtype=torch.int64).view(n, 1)
+    off = f - st.view(1, -1)
+    cost = (2 * off - (L - 1)).abs()
+    cost = torch.where((off >= 0) & (off < L), cost, torch.full_like(cost, 4 * MAX_LABEL_WINDOW))
+    # the FIRST minimum (ties go to the lower window): the smallest of cost * W + k
+    owner = (cost * len(starts) + torch.arange(len(starts)).view(1, -1)).min(dim=1).values % len(starts)
+    return LabelWindows(st.to(torch.int32), L, owner.to(torch.int32))
+
+
+def idm_feature_plan(n_frames: int, window: int, stride: int) -> IDMFeaturePlan:
+    """Which per-frame IDM features a labelling pass must compute, once each.  Everything in front of the transformer blocks is per-frame work
+    except the temporal Conv3d(5,1,1), which zero-pads at the edges of ITS window (lib/policy.py:394-403): row (window k, offset o), frame
+    f = s_k + o, sees the frames [max(s_k, f - 2), min(s_k + L, f + 3)) and nothing else of the window.  Rows with the same key
+    (f, that lower bound, that upper bound) have identical features -- all but the two rows at either end of a window share the interior
+    key (f, f - 2, f + 3) with every other window that holds f.  The distinct keys, sorted, are the slots: at most n_frames + 4 W of them,
+    against W L window rows.
+    -> label_windows' fields plus src, lo, hi int32 [n_slots] (ops.conv3d_t5_indexed), win_rows int32 [W L] (the slot of every window row)
+    and sel_rows int32 [n_frames] (the window row k L + o that labels each frame).  CPU tensors."""
+    starts, L, owner = label_windows(n_frames, window, stride)
+    n, W = int(n_frames), starts.numel()
+    s = starts.to(torch.int64).view(W, 1)
+    f = s + torch.arange(L, dtype=torch.int64).view(1, L)                     # [W, L]
+    lo = torch.maximum(s.expand(W, L), f - 2)
+    hi = torch.minimum((s + L).expand(W, L), f + 3)
+    # one sortable integer per key: the bounds as their offsets from f (2 - (f - lo) in 0..2, hi - f - 1 in 0..2)
+    key = (f * 3 + (lo - f + 2)) * 3 + (hi - f - 1)
+    uniq, inverse = torch.unique(key.reshape(-1), sorted=True, return_inverse=True)
+    src = uniq // 9
+    slot_lo = src + (uniq // 3) % 3 - 2
+    slot_hi = src + uniq % 3 + 1
+    assert uniq.numel() <= n + 4 * W
+    own = owner.to(torch.int64)
+    sel = own * L + (torch.arange(n, dtype=torch.int64) - starts.to(torch.int64)[own])
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    return IDMFeaturePlan(n, int(window), int(stride), starts, L, owner, i32(src), i32(slot_lo), i32(slot_hi), i32(inverse), i32(sel))
 
 
 def bc_loss_metrics(lp_buttons, lp_camera, act_buttons, act_camera, weight=None):
