@@ -80,11 +80,12 @@ int vpt_chw_to_blocked(const float* src, float* dst, int64_t rows, int C, int H,
  *   VPT_WS_ATTENTION_BACKWARD_DBND (B, t, heads, maxlen, -)  ... and its dbnd_slab
  *   VPT_WS_FRAME_AFFINE_BACKWARD (frames, HW, per_element, pass, C)   vpt_frame_affine_backward's partials for that pass
  *   VPT_WS_CONV_FIRST_BACKWARD   (frames, H, W, -, Cout)     vpt_conv_first_backward's partials (depends on the device's CU count)
- *   VPT_WS_BC_LOSS               (M, -, -, -, -)             vpt_bc_loss's workspace (the record slab + its reduction scratch)
+ *   VPT_WS_BC_LOSS               (M, -, -, -, -)             vpt_bc_loss's / vpt_idm_loss's workspace (the record slab + its reduction scratch)
+ *   VPT_WS_FULL_ATTENTION_BACKWARD (B, t, hid, -, -)         vpt_full_attention_backward's dkv_slab (one slot per 32-query tile)
  * Returns -1 for an unknown op. */
 enum { VPT_WS_CONV3X3_WGRAD = 1, VPT_WS_CONV_BACKWARD_PREPARE = 2, VPT_WS_LINEAR_SPLITK = 3, VPT_WS_LAYERNORM_BACKWARD = 4, VPT_WS_COLUMN_SUM = 5,
        VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9,
-       VPT_WS_BC_LOSS = 10 };
+       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11 };
 int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout);
 int vpt_pack_conv3x3(const float* weight, const float* gain, const float* bias, void* wpk, float* edge_sa, float* edge_sg,
                      int Cout, int Cin, void* stream);
@@ -407,6 +408,31 @@ int vpt_masked_attention_backward(const float* qkvr, const float* kmem, const fl
 int vpt_masked_attention_backward_episodes(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
                                            const float* b_nd, const float* dout, float* dqkvr, float* db_nd, float* dkv_slab, float* dbnd_slab,
                                            const int32_t* qlo, int B, int t, int heads, int hid, int ld, int maxlen, void* stream);
+
+/* ---- inverse-dynamics model training (everything behind the CNN; the reference has no IDM training script, the gradients are what torch
+ * autograd gives for InverseActionNet.forward, lib/policy.py:374-392) ---- */
+
+/* Backward of vpt_masked_attention_forward with causal = 0, maxlen = 0 -- mask "none" (lib/masked_attention.py:137-141: no band mask, an empty
+ * memory) through lib/xf.py:18-63 (softmax(Q K^T / d_head) V per head, d_head = 128): every query sees all t <= 160 rows of its window.
+ *   qkv fp32 [B*t][ld] (Q, K, V at columns 0, hid, 2 hid; ld >= 3 hid, ld % 4 == 0), dout fp32 [B*t][hid] -> dqkv fp32 [B*t][ld]: dQ, dK, dV, and
+ *   zeros in the columns >= 3 hid (every element written, nothing to zero).
+ * The probabilities are recomputed from qkv (the forward keeps nothing); all contractions run on the fp32 matrix cores.  Every 32-query tile writes
+ * its piece of dK / dV to its own slot of dkv_slab (VPT_WS_FULL_ATTENTION_BACKWARD (B, t, hid) bytes) and the slots are added in slot order: no
+ * atomics, the same inputs give the same bits, and a window's result does not depend on the other windows of the call. */
+int vpt_full_attention_backward(const float* qkv, const float* dout, float* dqkv, float* dkv_slab,
+                                int B, int t, int heads, int hid, int ld, void* stream);
+
+/* The IDM's loss, its gradient and its metrics in one launch: gb independent nb-way button groups and gc nc-way camera groups per frame
+ * (lib/action_head.py:136-160: a CategoricalActionHead of shape (20, 2) / (2, 11)),
+ *   loss = sum_rows w (nll_b + nll_c) / sum_rows w,  nll_* = -sum over the head's groups of the label's log-prob (lib/action_head.py:176-184,252-253).
+ * lp_buttons fp32 [M][gb][nb], lp_camera fp32 [M][gc][nc], act_buttons int64 [M][gb], act_camera int64 [M][gc], weight fp32 [M] or NULL.  Outputs as
+ * vpt_bc_loss (each optional): dz 16-bit [M][ldz], ldz >= gb nb + gc nc, (exp(lp) - onehot) * (scale * weight[row]) in the column order of the two head
+ * matrices concatenated, further columns zero; frame_out fp32 [M][8] = nll_b, nll_c, ent_b, ent_c (sums over the groups), hit_b, hit_c (fraction of
+ * the head's groups whose arg-max, lowest index on ties, is the label), w, 0; totals fp32 [8] through `workspace` (VPT_WS_BC_LOSS (M) bytes,
+ * M <= 65536) in a fixed order.  A row with weight 0 stores exact zeros in dz and adds exact zeros to totals; labels are only compared. */
+int vpt_idm_loss(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons, const int64_t* act_camera,
+                 const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
+                 int M, int gb, int nb, int gc, int nc, int ldz, float scale, void* stream);
 
 /* ---- backward of the IMPALA CNN (behavioural_cloning.py:117-119 obtains these from torch autograd) ---- */
 

@@ -1,0 +1,91 @@
+"""One IDM fine-tuning step against one IDM forward on the same batch: how much the trained part (everything behind the frozen CNN) adds.
+python tools/idm_train_bench.py [--batch 8] [--window 128] [--rounds 5] [--model 4x] [--precisions bf16,fp16] [--out idm_train_bench.json]
+
+IDMTrainer.step (frozen temporal conv + CNN through the inference path, saving forward of the trunk, ops.idm_loss, the hand-written backward,
+one-launch Adam) and IDMEngine.forward in ONE process per precision, after a warm-up of each, alternating (step, forward, forward, step, ...) so
+that a drift of the box's clock hits both alike; every pass is timed with HIP events around the whole call.  The forward right behind a step
+re-packs the weights the step changed; the second forward is the steady one, and their difference is what a loop of steps pays per step on top
+of `step_ms`.  The spread reported is the first forward's own (max - min) / median over its rounds.  --profile-steps N instead runs N untimed steps and nothing else: the pass to put under
+`rocprofv3 --kernel-trace --stats` for the attention backward's own time (a run of its own, never together with the timing above).
+Prints one JSON line per precision; needs a GPU."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+torch.set_grad_enabled(False)
+import __graft_entry__ as ge
+
+ge.build()
+from bench import BoxSampler
+from vpt_amd import configs
+from vpt_amd.idm_training import IDMTrainer
+from vpt_amd.lib.policy import InverseActionPolicy
+from vpt_amd.lib.types import idm_action_space
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--batch", type=int, default=8)
+ap.add_argument("--window", type=int, default=128)
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--model", default="4x")
+ap.add_argument("--precisions", default="bf16,fp16")
+ap.add_argument("--profile-steps", type=int, default=0)
+ap.add_argument("--out", default=None)
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("idm_train_bench: no GPU (a step time is a GPU measurement; there is no CPU figure)")
+
+g = torch.Generator().manual_seed(1)
+img = torch.randint(0, 256, (a.batch, a.window, 128, 128, 3), generator=g, dtype=torch.uint8).to("cuda")
+buttons = torch.randint(0, 2, (a.batch, a.window, 20), generator=g).to("cuda")
+camera = torch.randint(0, 11, (a.batch, a.window, 2), generator=g).to("cuda")
+results = []
+for prec in a.precisions.split(","):
+    pol = InverseActionPolicy(idm_action_space(), pi_head_kwargs=dict(temperature=2.0), idm_net_kwargs=configs.idm_kwargs_for(a.model), precision=prec)
+    configs.randomize_(pol, 0)
+    pol = pol.to("cuda")
+    tr = IDMTrainer(pol, lr=1e-5, weight_decay=0.0)
+    run = {"step": lambda: tr.step(img, buttons, camera), "forward": lambda: (pol._ensure_packed(), pol._engine.forward(img))}
+    if a.profile_steps:
+        for _ in range(a.profile_steps):
+            run["step"]()
+        torch.cuda.synchronize()
+        continue
+    for k in ("step", "forward"):          # warm-up: every shape of the timed passes, both paths
+        run[k]()
+    torch.cuda.synchronize()
+    # a step leaves the packed weights stale and the NEXT call re-packs them (IDMEngine.pack): in the alternation that is the forward right behind
+    # the step, so a second forward is timed behind it -- "forward" carries one pack, "forward_steady" none, and a loop of steps pays step + pack
+    ms = {"step": [], "forward": [], "forward_steady": []}
+    with BoxSampler(torch.cuda.current_device()) as box:
+        for _ in range(a.rounds):
+            for k in ("step", "forward", "forward_steady"):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                run[k.split("_")[0]]()
+                e1.record()
+                e1.synchronize()
+                ms[k].append(e0.elapsed_time(e1))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    pack_ms = med["forward"] - med["forward_steady"]
+    rec = dict(tool="idm_train_bench", model=a.model, precision=prec, batch=a.batch, window=a.window, rounds=a.rounds,
+               trainable_params=int(sum(tr.params[n].numel() for n in tr.trainable)), params=int(sum(p.numel() for p in tr.params.values())),
+               step_ms=[round(x, 2) for x in ms["step"]], forward_ms=[round(x, 2) for x in ms["forward"]],
+               step_ms_median=round(med["step"], 2), forward_ms_median=round(med["forward"], 2),
+               step_over_forward=round(med["step"] / med["forward"], 4),
+               forward_steady_ms=[round(x, 2) for x in ms["forward_steady"]], forward_steady_ms_median=round(med["forward_steady"], 2),
+               repack_ms=round(pack_ms, 2), step_plus_repack_over_forward_steady=round((med["step"] + pack_ms) / med["forward_steady"], 4),
+               forward_spread=round((max(ms["forward"]) - min(ms["forward"])) / med["forward"], 4),
+               step_frames_per_s=round(a.batch * a.window / med["step"] * 1e3, 1), steps_taken=tr.step_count, steps_skipped=tr.skipped_steps, box=box.record())
+    print(json.dumps(rec), flush=True)
+    results.append(rec)
+    del pol, tr, run
+    torch.cuda.empty_cache()
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(results, f, indent=1)

@@ -143,6 +143,87 @@ extern "C" int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The inverse-dynamics model's loss: gb independent nb-way button groups and gc nc-way camera groups per frame (20 x 2 and 2 x 11 in the released
+// model), loss = sum_rows w (nll_b + nll_c) / sum_rows w with nll_* summed over the head's groups -- the negative of DictActionHead.logprob
+// (lib/action_head.py:176-184,252-253).  One wavefront per frame: the elementwise pass writes dz in the column order of the two head matrices
+// concatenated ([group][class], buttons first; vpt_bc_loss_kernel's element arithmetic), then lane g takes group g -- its label's log-prob, its
+// entropy, its arg-max -- and the head sums are wave reductions (a fixed shuffle tree).  The record layout, the zero-weight rule and the totals
+// (slab row per frame + vpt_slab_sum) are vpt_bc_loss_kernel's.
+__global__ __launch_bounds__(256) void vpt_idm_loss_kernel(VptIdmLossArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.M) return;                                    // (wave-uniform: the shuffles below see whole waves)
+  const int nbt = a.gb * a.nb, nct = a.gc * a.nc;
+  const float* lb = a.lp_buttons + (size_t)row * nbt;
+  const float* lc = a.lp_camera + (size_t)row * nct;
+  const long* ab = a.act_buttons + (size_t)row * a.gb;
+  const long* ac = a.act_camera + (size_t)row * a.gc;
+  const float w = a.weight ? a.weight[row] : 1.f;
+  const bool live = w != 0.f;
+  const float rs = a.scale * w;
+  if (a.dz) {
+    vpt_op16* dz = a.dz + (size_t)row * a.ldz;
+    for (int i = lane; i < a.ldz; i += 64) {
+      float g = 0.f;
+      if (i < nbt) {
+        const int grp = i / a.nb, c = i - grp * a.nb;
+        g = bc_loss_grad(expf(lb[i]), (long)c == ab[grp], rs);
+      } else if (i < nbt + nct) {
+        const int j = i - nbt, grp = j / a.nc, c = j - grp * a.nc;
+        g = bc_loss_grad(expf(lc[j]), (long)c == ac[grp], rs);
+      }
+      dz[i] = (vpt_op16)(live ? g : 0.f);
+    }
+  }
+  if (!a.frame_out && !a.slab) return;
+  float pb = 0.f, pc = 0.f, eb = 0.f, ec = 0.f, hb = 0.f, hc = 0.f;      // the label's lp, sum p lp and the hits, per head
+  for (int grp = lane; grp < a.gb + a.gc; grp += 64) {
+    const bool cam = grp >= a.gb;
+    const int gi = cam ? grp - a.gb : grp, n = cam ? a.nc : a.nb;
+    const float* l = cam ? lc + gi * a.nc : lb + gi * a.nb;
+    const long lab = cam ? ac[gi] : ab[gi];
+    float e = 0.f, pick = 0.f, mv = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int c = 0; c < n; ++c) {
+      const float lv = l[c], p = expf(lv);
+      e += (p == 0.f) ? 0.f : p * lv;
+      if ((long)c == lab) pick += lv;
+      argmax_take(mv, mi, lv, c);
+    }
+    const float hit = (lab >= 0 && lab < n && (long)mi == lab) ? 1.f : 0.f;
+    if (cam) { pc += pick; ec += e; hc += hit; }
+    else { pb += pick; eb += e; hb += hit; }
+  }
+  pb = wave_sum(pb); pc = wave_sum(pc); eb = wave_sum(eb); ec = wave_sum(ec); hb = wave_sum(hb); hc = wave_sum(hc);
+  if (lane != 0) return;
+  // [nll_b, nll_c, ent_b, ent_c, hit_b, hit_c, w, 0]: the frame's own (unweighted) values; a hit is the fraction of the head's groups
+  const float rec[8] = {-pb, -pc, -eb, -ec, hb / (float)a.gb, hc / (float)a.gc, w, 0.f};
+  if (a.frame_out) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a.frame_out[(size_t)row * 8 + k] = rec[k];
+  }
+  if (a.slab) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a.slab[(size_t)row * 8 + k] = live ? w * rec[k] : 0.f;
+    a.slab[(size_t)row * 8 + 6] = live ? w : 0.f;
+    a.slab[(size_t)row * 8 + 7] = (w > 0.f) ? 1.f : 0.f;
+  }
+}
+
+extern "C" int vpt_idm_loss_launch(const VptIdmLossArgs* a, float* totals, float* workspace, hipStream_t stream) {
+  if (a->M <= 0 || a->gb <= 0 || a->nb <= 0 || a->gc <= 0 || a->nc <= 0) return -1;
+  if (a->dz && a->ldz < a->gb * a->nb + a->gc * a->nc) return -1;
+  if (totals && !workspace) return -1;
+  if (totals && a->M > 65536) return -2;        // vpt_slab_sum: at most 256 slices of 256 rows
+  VptIdmLossArgs k = *a;
+  k.slab = totals ? workspace : nullptr;
+  hipLaunchKernelGGL(vpt_idm_loss_kernel, dim3((a->M + 3) / 4), dim3(256), 0, stream, k);
+  if (hipGetLastError() != hipSuccess) return -3;
+  if (!totals) return 0;
+  return vpt_slab_sum_launch(workspace, a->M, 8, 8L, totals, 8, nullptr, 0, workspace + 8L * a->M, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Backward of lp = log_softmax(z / T) for an ARBITRARY incoming gradient g = dL/dlp (what torch autograd hands to the
 // policy's outputs, lib/policy.py:271-305): dz = (g - exp(lp) * sum_j g_j) / T per head; the value column passes through.
 // One workgroup per row; the row sums by wave shuffles + LDS.
@@ -683,4 +764,218 @@ extern "C" int vpt_attn_bwd_launch(const VptAttnBwdArgs* a, hipStream_t stream) 
   if (hipGetLastError() != hipSuccess) return -3;
   return vpt_slab_sum_launch(a->dbnd_slab, (int)rows, 10 * a->maxlen, 10L * a->maxlen, a->db_nd, 10 * a->maxlen, nullptr, 1,
                              a->dbnd_slab + rows * 10 * a->maxlen, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Backward of vpt_attn_kernel with causal = 0 -- the inverse-dynamics model's attention (mask "none", lib/masked_attention.py:139-141, lib/xf.py
+// with maxlen = 0): every query of a window sees all t <= 160 rows of the window, no memory, no relative-position bias.
+//   out_i = sum_j P_ij V_j,  P = softmax_j(Q_i . K_j / d_h);  D_i = sum_j P_ij (dO_i . V_j);  dS = P (dP - D);
+//   dQ = dS K / d_h;  dK = dS^T Q / d_h;  dV = P^T dO.
+// One workgroup per (window, head, 32-query tile), the contractions on the fp32 matrix cores exactly as vpt_attn_bwd_kernel lays them out (same
+// lane -> operand maps; P is recomputed from qkv, the forward keeps nothing).  Rows >= t of a partial tile load zeros, their scores are masked,
+// so they add exact zeros to every sum.  Every key is reached by all ceil(t / 32) query tiles: tile q writes its piece of dK / dV to slab slot q
+// and vpt_full_attn_bwd_finish_kernel adds the slots in slot order -- no atomics, the grid is a function of (B, t, heads) alone and a window's
+// workgroups read and write that window's rows only, so a window's result does not depend on its neighbours.
+#define FA_P_OFF 0                                        // P  [32][ATT_SS]
+#define FA_D_OFF (FA_P_OFF + ATT_QT * ATT_SS)             // dP, then dS  [32][ATT_SS]
+#define FA_PT_OFF (FA_D_OFF + ATT_QT * ATT_SS)            // partial tiles of key tile 4: [wave][16][64]
+#define FA_FLOATS (FA_PT_OFF + 4 * 16 * 64)               // 58 368 bytes: two workgroups per CU
+
+__global__ __launch_bounds__(256, 2) void vpt_full_attn_bwd_kernel(VptFullAttnBwdArgs a) {
+  __shared__ __attribute__((aligned(16))) float sm[FA_FLOATS];
+  float* Ps = sm + FA_P_OFF;
+  float* Ds = sm + FA_D_OFF;
+  float* Pt = sm + FA_PT_OFF;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, hi = lane >> 5;
+  const int b = blockIdx.y / a.heads, h = blockIdx.y - b * a.heads;
+  const int q0 = blockIdx.x * ATT_QT;
+  const int t = a.t, hid = a.hid;
+  const size_t tok0 = (size_t)b * t;
+  const float inv_dh = 1.0f / ATT_DH;
+  const float* qbase = a.qkv + (tok0 + q0) * a.ld + h * ATT_DH;          // this tile's Q rows / dO rows, this head
+  const float* dobase = a.dout + (tok0 + q0) * hid + h * ATT_DH;
+  const float* kbase = a.qkv + tok0 * a.ld + hid + h * ATT_DH;           // the window's K rows; V sits hid columns further
+  const int nq_valid = t - q0;                                           // queries q0 + qi with qi < nq_valid exist
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  // accumulator register r of a lane = row (r & 3) + 8 (r >> 2) + 4 hi of the 32 x 32 tile, column l31
+#define FA_ROW_OF(r_) (((r_) & 3) + 8 * ((r_) >> 2) + 4 * hi)
+
+  // QK-like contraction (M = queries, N = keys, K = d_head): key tiles 0..3 belong to waves 0..3, tile 4 (keys 128..159) is split over the waves
+  // by d and summed through Pt.  emit(key, r, value) receives the tile.  voff: 0 = the K rows, hid = the V rows.
+  auto qk_like = [&](const float* arow, int voff, auto emit) __attribute__((always_inline)) {
+    f32x16 acc, acc4;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc4[r] = 0.f; }
+    const int k0 = w * 32 + l31, k4 = 128 + l31;
+    const float* qa = arow ? arow + 4 * hi : nullptr;
+    const float* kb = (k0 < t) ? kbase + (size_t)k0 * a.ld + voff + 4 * hi : nullptr;
+    const float* kb4 = (k4 < t) ? kbase + (size_t)k4 * a.ld + voff + 4 * hi : nullptr;
+#pragma unroll 8
+    for (int g = 0; g < 16; ++g) {
+      const f32x4 q4 = qa ? *(const f32x4*)(qa + 8 * g) : z4, k4v = kb ? *(const f32x4*)(kb + 8 * g) : z4;
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.x, k4v.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.y, k4v.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.z, k4v.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.w, k4v.w, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const int g = 4 * w + g4;
+      const f32x4 q4 = qa ? *(const f32x4*)(qa + 8 * g) : z4, k4v = kb4 ? *(const f32x4*)(kb4 + 8 * g) : z4;
+      acc4 = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.x, k4v.x, acc4, 0, 0, 0);
+      acc4 = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.y, k4v.y, acc4, 0, 0, 0);
+      acc4 = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.z, k4v.z, acc4, 0, 0, 0);
+      acc4 = __builtin_amdgcn_mfma_f32_32x32x2f32(q4.w, k4v.w, acc4, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) Pt[(w * 16 + r) * 64 + lane] = acc4[r];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) emit(w * 32 + l31, r, acc[r]);
+#pragma unroll
+    for (int r4 = 0; r4 < 4; ++r4) {   // key tile 4: this wave finishes accumulator registers 4 w .. 4 w + 3
+      const int r = 4 * w + r4;
+      emit(128 + l31, r, (Pt[(0 * 16 + r) * 64 + lane] + Pt[(1 * 16 + r) * 64 + lane]) + (Pt[(2 * 16 + r) * 64 + lane] + Pt[(3 * 16 + r) * 64 + lane]));
+    }
+    __syncthreads();
+  };
+
+  // ---- 1. logits (as the forward kernel: dot / d_h where query and key exist) -> Ps ----
+  qk_like((l31 < nq_valid) ? qbase + l31 * a.ld : nullptr, 0, [&](int kk, int r, float dot) {
+    const int qi = FA_ROW_OF(r);
+    Ps[qi * ATT_SS + kk] = (qi < nq_valid && kk < t) ? dot * inv_dh : -3.0e38f;
+  });
+  // ---- softmax -> normalised P in Ps (8 rows per wave); a row that does not exist is all zeros ----
+  for (int r = w * 8; r < w * 8 + 8; ++r) {
+    float* srow = Ps + r * ATT_SS;
+    const float s0 = srow[lane], s1 = srow[lane + 64], s2 = (lane + 128 < ATT_NK) ? srow[lane + 128] : -3.0e38f;
+    const float m = wave_max(fmaxf(s0, fmaxf(s1, s2)));
+    const float e0 = (s0 > -1.0e38f) ? expf(s0 - m) : 0.f;
+    const float e1 = (s1 > -1.0e38f) ? expf(s1 - m) : 0.f;
+    const float e2 = (s2 > -1.0e38f) ? expf(s2 - m) : 0.f;
+    const float tot = wave_sum(e0 + e1 + e2);
+    const float inv = (tot > 0.f) ? 1.0f / tot : 0.f;
+    srow[lane] = e0 * inv;
+    srow[lane + 64] = e1 * inv;
+    if (lane + 128 < ATT_NK) srow[lane + 128] = e2 * inv;
+  }
+  // ---- 2. dP = dO V^T -> Ds (its trailing barrier also publishes P) ----
+  qk_like((l31 < nq_valid) ? dobase + l31 * hid : nullptr, hid, [&](int kk, int r, float dot) { Ds[FA_ROW_OF(r) * ATT_SS + kk] = dot; });
+  // ---- 3. D_i = sum_k P dP;  dS = P (dP - D_i) -> Ds (0 where the key or the query does not exist since P = 0) ----
+  for (int r = w * 8; r < w * 8 + 8; ++r) {
+    const float* prow = Ps + r * ATT_SS;
+    float* drow = Ds + r * ATT_SS;
+    const float p0 = prow[lane], p1 = prow[lane + 64], p2 = (lane + 128 < ATT_NK) ? prow[lane + 128] : 0.f;
+    const float d0 = drow[lane], d1 = drow[lane + 64], d2 = (lane + 128 < ATT_NK) ? drow[lane + 128] : 0.f;
+    const float Di = wave_sum(fmaf(p0, d0, fmaf(p1, d1, p2 * d2)));
+    drow[lane] = p0 * (d0 - Di);
+    drow[lane + 64] = p1 * (d1 - Di);
+    if (lane + 128 < ATT_NK) drow[lane + 128] = p2 * (d2 - Di);
+  }
+  __syncthreads();
+
+  const int dcol = w * 32 + l31;        // wave w owns d_head slice 32 w .. 32 w + 31 from here on
+  // dV-like contraction (M = keys, N = d_head, K = the tile's queries): piece[key][d] = scale * sum_query X[query][key] Y[query][d] -> this query
+  // tile's slab slot, column block `cb` (0: dK, 1: dV).  Key tiles beyond the window are skipped (wave-uniform).
+  auto dv_like = [&](const float* X, const float* ybase, int ystride, int cb, float scale) __attribute__((always_inline)) {
+    f32x16 acc[5];
+#pragma unroll
+    for (int kt = 0; kt < 5; ++kt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[kt][r] = 0.f;
+#pragma unroll 1
+    for (int g = 0; g < 4; ++g) {
+      float y[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int qi = 8 * g + 4 * hi + e;          // this lane's query row of the k step
+        y[e] = (qi < nq_valid) ? ybase[qi * ystride + dcol] : 0.f;
+      }
+#pragma unroll
+      for (int kt = 0; kt < 5; ++kt) {
+        if (kt * 32 < t) {
+          const float* xc = X + (8 * g + 4 * hi) * ATT_SS + kt * 32 + l31;     // A: row = key, k = queries 8 g + 4 hi + e
+          acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[0], y[0], acc[kt], 0, 0, 0);
+          acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[ATT_SS], y[1], acc[kt], 0, 0, 0);
+          acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[2 * ATT_SS], y[2], acc[kt], 0, 0, 0);
+          acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(xc[3 * ATT_SS], y[3], acc[kt], 0, 0, 0);
+        }
+      }
+    }
+    // wave-uniform base + one 32-bit per-lane index per element (the launcher checks that the slab fits 31 bits)
+    float* colbase = a.dkv_slab + ((size_t)blockIdx.x * a.B * t + tok0) * (2 * hid) + cb * hid + h * ATT_DH;
+#pragma unroll
+    for (int kt = 0; kt < 5; ++kt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int jr = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+        asm volatile("" : "+v"(jr));     // keep the row test next to its store (vpt_attn_bwd_kernel: hoisted, the 80 lane masks spill)
+        if (jr < t) colbase[jr * (2 * hid) + dcol] = acc[kt][r] * scale;
+      }
+  };
+  // ---- 4. dV piece = P^T dO ;  5. dK piece = dS^T Q / d_h ----
+  dv_like(Ps, dobase, hid, 1, 1.0f);
+  dv_like(Ds, qbase, a.ld, 0, inv_dh);
+  // ---- 6. dQ = dS K / d_h (PV-like: M = queries, N = d_head, K = keys) ----
+  {
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+    const float* pa = Ds + l31 * ATT_SS + 4 * hi;
+#pragma unroll 2
+    for (int g = 0; g < ATT_NK / 8; ++g) {
+      const f32x4 p4 = *(const f32x4*)(pa + 8 * g);
+      float v[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int j = 8 * g + 4 * hi + e;
+        v[e] = (j < t) ? kbase[(size_t)j * a.ld + dcol] : 0.f;
+      }
+      o = __builtin_amdgcn_mfma_f32_32x32x2f32(p4.x, v[0], o, 0, 0, 0);
+      o = __builtin_amdgcn_mfma_f32_32x32x2f32(p4.y, v[1], o, 0, 0, 0);
+      o = __builtin_amdgcn_mfma_f32_32x32x2f32(p4.z, v[2], o, 0, 0, 0);
+      o = __builtin_amdgcn_mfma_f32_32x32x2f32(p4.w, v[3], o, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qi = FA_ROW_OF(r);
+      if (qi < nq_valid) a.dqkv[(tok0 + q0 + qi) * a.ld + h * ATT_DH + dcol] = o[r] * inv_dh;
+    }
+  }
+#undef FA_ROW_OF
+}
+
+// dqkv[token][hid .. ld): dK and dV = the sum over the ceil(t / 32) slab slots in slot order, zeros in the columns >= 3 hid.  One thread per float4.
+__global__ __launch_bounds__(256) void vpt_full_attn_bwd_finish_kernel(VptFullAttnBwdArgs a) {
+  const int c4n = (a.ld - a.hid) >> 2, kv4 = (2 * a.hid) >> 2;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)a.B * a.t * c4n) return;
+  const long tok = i / c4n;
+  const int c4 = (int)(i - tok * c4n);
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  if (c4 < kv4) {
+    const int slots = (a.t + ATT_QT - 1) / ATT_QT;
+    const size_t slot_stride = (size_t)a.B * a.t * 2 * a.hid;
+    const float* p = a.dkv_slab + (size_t)tok * (2 * a.hid) + 4 * c4;
+    for (int sl = 0; sl < slots; ++sl) {
+      const f32x4 v = *(const f32x4*)(p + sl * slot_stride);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  }
+  *(f32x4*)(a.dqkv + (size_t)tok * a.ld + a.hid + 4 * c4) = s;
+}
+
+extern "C" long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid) { return (long)((t + ATT_QT - 1) / ATT_QT) * B * t * 2 * hid; }
+
+extern "C" int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t stream) {
+  if (a->B <= 0 || a->t < 1 || a->t > ATT_NK || a->heads <= 0 || a->hid != a->heads * ATT_DH || a->ld < 3 * a->hid || (a->ld & 3)) return -1;
+  if (!a->qkv || !a->dout || !a->dqkv || !a->dkv_slab) return -1;
+  if (vpt_full_attn_bwd_dkv_floats(a->B, a->t, a->hid) > 0x7fffffffL || (long)a->B * a->heads > 65535) return -2;       // 32-bit slab indices, grid.y
+  dim3 grid((a->t + ATT_QT - 1) / ATT_QT, a->B * a->heads);
+  hipLaunchKernelGGL(vpt_full_attn_bwd_kernel, grid, dim3(256), 0, stream, *a);
+  const long n4 = (long)a->B * a->t * ((a->ld - a->hid) >> 2);
+  hipLaunchKernelGGL(vpt_full_attn_bwd_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -80,6 +80,7 @@ int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout)
     case VPT_WS_FRAME_AFFINE_BACKWARD: return 4 * (int64_t)vpt_affine_bwd_partial_floats(frames, Cout / 32, H, W, Cin);   /* (frames, HW, per_element, pass, C) */
     case VPT_WS_CONV_FIRST_BACKWARD: return 4 * (int64_t)vpt_conv_first_bwd_partial_floats(frames, H, W, Cout);
     case VPT_WS_BC_LOSS: return 4 * (int64_t)vpt_bc_loss_workspace_floats(frames);                          /* (M) */
+    case VPT_WS_FULL_ATTENTION_BACKWARD: return 4 * (int64_t)vpt_full_attn_bwd_dkv_floats(frames, H, W);    /* (B, t, hid) */
     case VPT_WS_LINEAR_SPLITK: return 4 * (int64_t)frames * H * (int64_t)W;   /* splitk (= frames) x M (= H) x N (= W) fp32 partial slices */
     default: return -1;
   }
@@ -550,6 +551,32 @@ int vpt_bc_loss(const float* lp_buttons, const float* lp_camera, const int64_t* 
   a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.act_buttons = (const long*)act_buttons; a.act_camera = (const long*)act_camera;
   a.weight = weight; a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz; a.scale = scale;
   CHECK_LAUNCH(vpt_bc_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_bc_loss");
+}
+
+int vpt_idm_loss(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons, const int64_t* act_camera,
+                 const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
+                 int M, int gb, int nb, int gc, int nc, int ldz, float scale, void* stream) {
+  if (!lp_buttons || !lp_camera || !act_buttons || !act_camera) return fail(-1, "vpt_idm_loss: null log-probs / labels");
+  if (M <= 0 || gb <= 0 || nb <= 0 || gc <= 0 || nc <= 0) return fail(-1, "vpt_idm_loss: M and the group shapes must be positive");
+  if (dz && ldz < gb * nb + gc * nc) return fail(-1, "vpt_idm_loss: ldz < gb * nb + gc * nc");
+  if (totals && !workspace) return fail(-1, "vpt_idm_loss: totals need the workspace (VPT_WS_BC_LOSS)");
+  VptIdmLossArgs a = {};
+  a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.act_buttons = (const long*)act_buttons; a.act_camera = (const long*)act_camera;
+  a.weight = weight; a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.gb = gb; a.nb = nb; a.gc = gc; a.nc = nc; a.ldz = ldz; a.scale = scale;
+  CHECK_LAUNCH(vpt_idm_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_idm_loss");
+}
+
+int vpt_full_attention_backward(const float* qkv, const float* dout, float* dqkv, float* dkv_slab,
+                                int B, int t, int heads, int hid, int ld, void* stream) {
+  if (!qkv || !dout || !dqkv) return fail(-1, "vpt_full_attention_backward: null pointer");
+  if (!dkv_slab) return fail(-1, "vpt_full_attention_backward: the dkv_slab workspace is required (VPT_WS_FULL_ATTENTION_BACKWARD)");
+  if (B <= 0 || t < 1) return fail(-1, "vpt_full_attention_backward: B and t must be positive");
+  if (t > 160) return fail(-1, "vpt_full_attention_backward: windows of at most 160 rows");
+  if (heads <= 0 || hid != heads * 128) return fail(-1, "vpt_full_attention_backward: hid must be heads * 128");
+  if ((ld & 3) || ld < 3 * hid) return fail(-1, "vpt_full_attention_backward: ld must be a multiple of 4 and at least 3 * hid");
+  VptFullAttnBwdArgs a = {};
+  a.qkv = qkv; a.dout = dout; a.dqkv = dqkv; a.dkv_slab = dkv_slab; a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld;
+  CHECK_LAUNCH(vpt_full_attn_bwd_launch(&a, (hipStream_t)stream), "vpt_full_attention_backward");
 }
 
 int vpt_heads_logprob_backward(const float* lp_buttons, const float* lp_camera, const float* g_buttons, const float* g_camera,

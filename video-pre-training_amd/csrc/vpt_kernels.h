@@ -313,6 +313,27 @@ struct VptBcLossArgs {      // weighted BC loss: gradient + per-frame records + 
   float scale;
 };
 
+struct VptIdmLossArgs {     // IDM loss over gb + gc independent categorical groups (vpt_idm_loss_kernel); outputs as VptBcLossArgs
+  const float* lp_buttons; // [M][gb][nb] log-probabilities (forward output)
+  const float* lp_camera;  // [M][gc][nc]
+  const long* act_buttons; // [M][gb]; only compared with class indices (an out-of-range label matches nothing)
+  const long* act_camera;  // [M][gc]
+  const float* weight;     // optional [M]
+  vpt_op16* dz;            // optional [M][ldz]: (exp(lp) - onehot) * (scale * weight[row]) in the column order [buttons ; camera], further columns zero
+  float* frame_out;        // optional [M][8]: nll_b, nll_c (sums over the groups), ent_b, ent_c, hit_b, hit_c (fraction of groups), w, 0
+  float* slab;             // set by the launcher: [M][8] weighted records
+  int M, gb, nb, gc, nc, ldz;
+  float scale;
+};
+
+struct VptFullAttnBwdArgs { // backward of vpt_attn_kernel with causal = 0 (mask "none", no memory, no bias): vpt_full_attn_bwd_kernel
+  const float* qkv;        // forward projections [B*t][ld]: Q | K | V
+  const float* dout;       // [B*t][hid]
+  float* dqkv;             // [B*t][ld]: dQ by the main kernel; dK, dV and zeros in the columns >= 3 hid by the finish kernel
+  float* dkv_slab;         // [ceil(t/32)][B*t][2 hid] workspace: every query tile's piece of dK / dV (vpt_full_attn_bwd_dkv_floats)
+  int B, t, heads, hid, ld;
+};
+
 struct VptHeadsBwdArgs {   // generic backward of the two log-softmax heads + the value column (autograd boundary)
   const float* lp_buttons; // [M][nb] log-probabilities (forward output)
   const float* lp_camera;  // [M][nc]
@@ -430,6 +451,9 @@ int vpt_pack_linear_launch(const float* w, void* out, int N, int K, int transpos
 int vpt_nll_bwd_launch(const VptNllBwdArgs* a, hipStream_t s);
 long vpt_bc_loss_workspace_floats(int M);
 int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* workspace, hipStream_t s);
+int vpt_idm_loss_launch(const VptIdmLossArgs* a, float* totals, float* workspace, hipStream_t s);
+int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t s);
+long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid);
 int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);
 int vpt_ln_bwd_launch(const VptLnBwdArgs* a, hipStream_t s);
 int vpt_gate_cast_launch(const VptGateCastArgs* a, hipStream_t s);

@@ -71,6 +71,8 @@ def _call(name, meta, *args, fmt="bf16", label=None):
 
 WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
 WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
+WS_FULL_ATTENTION_BACKWARD = 11
+FULL_ATTENTION_MAX_T = 160      # the mask="none" attention kernels' longest window (forward and backward)
 
 
 def _workspace(op, a=0, b=0, c=0, d=0, e=0, device=None, fmt="bf16"):
@@ -894,6 +896,48 @@ def masked_attention_backward(qkvr, kmem, vmem, memvalid, b_nd, dout, db_nd, bat
     _call("vpt_masked_attention_backward", dict(flops=10.0 * batch * t * (t + kmem.shape[1]) * hid), ptr(qkvr), ptr(kmem), ptr(vmem),
           ptr(memvalid), ptr(b_nd), ptr(dout), ptr(dqkvr), ptr(db_nd), ptr(dkv), ptr(dbnd), batch, t, heads, hid, qkvr.shape[1], kmem.shape[1], _stream())
     return dqkvr
+
+
+def full_attention_backward(qkv, dout, batch, t, heads, hid):
+    """Backward of full_attention (mask "none", no memory): qkv fp32 [B*t, ld], dout fp32 [B*t, hid] -> dqkv fp32 [B*t, ld] (dQ | dK | dV, zeros in
+    the columns >= 3 hid; every element written).  Bit-reproducible; a window's rows do not depend on the other windows of the call."""
+    _chk(qkv, torch.float32, "qkv"); _chk(dout, torch.float32, "dout")
+    if t > FULL_ATTENTION_MAX_T:
+        raise NotImplementedError(f"the mask='none' attention backward handles windows of at most {FULL_ATTENTION_MAX_T} frames, got {t}")
+    if qkv.dim() != 2 or qkv.shape[0] != batch * t or tuple(dout.shape) != (batch * t, hid):
+        raise ValueError(f"full_attention_backward: qkv must be [{batch * t}, ld] and dout [{batch * t}, {hid}], got {tuple(qkv.shape)} and {tuple(dout.shape)}")
+    dqkv = torch.empty_like(qkv)
+    slab = _workspace(WS_FULL_ATTENTION_BACKWARD, batch, t, hid, device=qkv.device)
+    _call("vpt_full_attention_backward", dict(flops=10.0 * batch * t * t * hid), ptr(qkv), ptr(dout), ptr(dqkv), ptr(slab),
+          batch, t, heads, hid, qkv.shape[1], _stream())
+    return dqkv
+
+
+def idm_loss(lp_buttons, lp_camera, act_buttons, act_camera, scale, weight=None, dtype=torch.bfloat16, want_dz=True, want_frames=True,
+             want_totals=True):
+    """The IDM's weighted loss in one sweep over the two heads' log-probs (vpt_idm_loss) -> (dz | None, frame_out | None, totals | None).
+    lp_buttons fp32 [M, G_b, n_b], lp_camera fp32 [M, G_c, n_c]; act_* int64 [M, G]; weight fp32 [M] or None (all ones).
+    dz: 16-bit [M, round_up(G_b n_b + G_c n_c, 64)] = scale * w_r * (exp(lp) - onehot), buttons first (padding and zero-weight rows: exact zeros);
+    frame_out fp32 [M, 8] = nll_b, nll_c, ent_b, ent_c (sums over the groups), hit_b, hit_c (fraction of groups), w, 0; totals fp32 [8] =
+    sum_r w frame_out[r, :6], sum w, rows with w > 0.  packing.idm_loss_metrics is the host twin."""
+    _chk(lp_buttons, torch.float32, "lp_buttons"); _chk(lp_camera, torch.float32, "lp_camera")
+    _chk(act_buttons, torch.int64, "act_buttons"); _chk(act_camera, torch.int64, "act_camera"); _chk(weight, torch.float32, "weight")
+    if lp_buttons.dim() != 3 or lp_camera.dim() != 3:
+        raise ValueError("idm_loss: log-probs must be [M, groups, classes]")
+    m, gb, nb = lp_buttons.shape
+    gc, nc = lp_camera.shape[1:]
+    if lp_camera.shape[0] != m or tuple(act_buttons.shape) != (m, gb) or tuple(act_camera.shape) != (m, gc) or (weight is not None and weight.numel() != m):
+        raise ValueError(f"idm_loss: labels must be [{m}, {gb}] / [{m}, {gc}] and weight [{m}]")
+    dt, fmt = _fmt(dtype=dtype)
+    dev = lp_buttons.device
+    ldz = (gb * nb + gc * nc + 63) // 64 * 64
+    dz = torch.empty(m, ldz, dtype=dt, device=dev) if want_dz else None
+    frame_out = torch.empty(m, 8, dtype=torch.float32, device=dev) if want_frames else None
+    totals = torch.empty(8, dtype=torch.float32, device=dev) if want_totals else None
+    ws = _workspace(WS_BC_LOSS, m, device=dev, fmt=fmt) if want_totals else None
+    _call("vpt_idm_loss", dict(bytes=(8.0 * (gb * nb + gc * nc) + (2.0 * ldz if want_dz else 0.0)) * m), ptr(lp_buttons), ptr(lp_camera), ptr(act_buttons),
+          ptr(act_camera), ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws), m, gb, nb, gc, nc, ldz, ctypes.c_float(scale), _stream(), fmt=fmt)
+    return dz, frame_out, totals
 
 
 def conv_backward_prepare(dy, y, res, stats_in, edge_sa, edge_sg, cin, dpooled=None, argmax=None, d_sa=None, d_sg=None, want_t12=False):

@@ -259,3 +259,45 @@ def bc_loss_metrics(lp_buttons, lp_camera, act_buttons, act_camera, weight=None)
     rec = torch.where(live, w.view(m, 1) * frame_out[:, :6], torch.zeros_like(frame_out[:, :6]))
     totals = torch.cat([rec.sum(0), torch.where(live.view(m), w, torch.zeros_like(w)).sum().view(1), (w > 0).sum().to(torch.float64).view(1)])
     return frame_out, totals
+
+
+def idm_loss_metrics(lp_buttons, lp_camera, act_buttons, act_camera, weight=None):
+    """Per-frame records and totals of the IDM's weighted loss -- the host twin of vpt_idm_loss_kernel (ops.idm_loss), in fp64 torch.  The IDM's heads
+    are independent categorical groups (lib/action_head.py:176-184: logprob = the groups' gathers, summed): lp_buttons [M, G_b, n_b],
+    lp_camera [M, G_c, n_c] log-probs; act_* int [M, G]; weight [M] or None (all ones).  Returns
+      frame_out fp64 [M, 8]: nll_b, nll_c, ent_b, ent_c -- sums over the head's groups; an entropy term with p == 0 counts 0 --, hit_b, hit_c -- the
+                 fraction of the head's groups whose arg-max (lowest index on ties) is the label; a label outside [0, n) picks nothing --, w, 0;
+      totals fp64 [8]: sum_rows w * frame_out[row, :6], sum w, number of rows with w > 0; a row with w == 0 adds exact zeros whatever it holds."""
+    m = lp_buttons.shape[0]
+    dev = lp_buttons.device
+    w = torch.ones(m, dtype=torch.float64, device=dev) if weight is None else weight.reshape(m).to(torch.float64)
+    cols = []
+    for lp, act in ((lp_buttons, act_buttons), (lp_camera, act_camera)):
+        lp = lp.to(torch.float64)
+        groups, n = lp.shape[1:]
+        act = act.reshape(m, groups, 1).to(torch.int64)
+        onehot = torch.arange(n, device=dev).view(1, 1, n) == act
+        nll = -torch.where(onehot, lp, torch.zeros_like(lp)).sum(dim=(1, 2))
+        p = lp.exp()
+        ent = -torch.where(p == 0, torch.zeros_like(lp), p * lp).sum(dim=(1, 2))
+        hit = (lp.argmax(-1, keepdim=True) == act).reshape(m, groups).to(torch.float64).mean(1)
+        cols.append((nll, ent, hit))
+    frame_out = torch.stack([cols[0][0], cols[1][0], cols[0][1], cols[1][1], cols[0][2], cols[1][2], w, torch.zeros_like(w)], dim=1)
+    live = (w != 0).view(m, 1)
+    rec = torch.where(live, w.view(m, 1) * frame_out[:, :6], torch.zeros_like(frame_out[:, :6]))
+    totals = torch.cat([rec.sum(0), torch.where(live.view(m), w, torch.zeros_like(w)).sum().view(1), (w > 0).sum().to(torch.float64).view(1)])
+    return frame_out, totals
+
+
+def idm_loss_grad(lp_buttons, lp_camera, act_buttons, act_camera, scale, weight=None):
+    """The host twin of ops.idm_loss's dz, unrounded and unpadded: fp64 [M, G_b n_b + G_c n_c] = scale * w_r * (exp(lp) - onehot), buttons first."""
+    m = lp_buttons.shape[0]
+    w = torch.ones(m, dtype=torch.float64, device=lp_buttons.device) if weight is None else weight.reshape(m).to(torch.float64)
+    parts = []
+    for lp, act in ((lp_buttons, act_buttons), (lp_camera, act_camera)):
+        lp = lp.to(torch.float64)
+        groups, n = lp.shape[1:]
+        onehot = torch.arange(n, device=lp.device).view(1, 1, n) == act.reshape(m, groups, 1).to(torch.int64)
+        g = (lp.exp() - onehot.to(torch.float64)) * (scale * w).view(m, 1, 1)
+        parts.append(torch.where((w != 0).view(m, 1, 1), g, torch.zeros_like(g)).reshape(m, groups * n))
+    return torch.cat(parts, 1)
