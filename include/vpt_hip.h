@@ -82,10 +82,11 @@ int vpt_chw_to_blocked(const float* src, float* dst, int64_t rows, int C, int H,
  *   VPT_WS_CONV_FIRST_BACKWARD   (frames, H, W, -, Cout)     vpt_conv_first_backward's partials (depends on the device's CU count)
  *   VPT_WS_BC_LOSS               (M, -, -, -, -)             vpt_bc_loss's / vpt_idm_loss's workspace (the record slab + its reduction scratch)
  *   VPT_WS_FULL_ATTENTION_BACKWARD (B, t, hid, -, -)         vpt_full_attention_backward's dkv_slab (one slot per 32-query tile)
+ *   VPT_WS_CONV3D_T5_BACKWARD    (frames, H, W, -, Cout)     vpt_conv3d_t5_backward's partials (one slab row per workgroup + the reduction's scratch)
  * Returns -1 for an unknown op. */
 enum { VPT_WS_CONV3X3_WGRAD = 1, VPT_WS_CONV_BACKWARD_PREPARE = 2, VPT_WS_LINEAR_SPLITK = 3, VPT_WS_LAYERNORM_BACKWARD = 4, VPT_WS_COLUMN_SUM = 5,
        VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9,
-       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11 };
+       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11, VPT_WS_CONV3D_T5_BACKWARD = 12 };
 int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout);
 int vpt_pack_conv3x3(const float* weight, const float* gain, const float* bias, void* wpk, float* edge_sa, float* edge_sg,
                      int Cout, int Cin, void* stream);
@@ -109,6 +110,17 @@ int vpt_conv_first_forward(const uint8_t* img, const void* wfrag, void* y, doubl
  * y: blocked [frames][Cout/32][H][W][32]; stats_out (optional) receives the statistics of y. */
 int vpt_conv3d_t5_forward(const uint8_t* img, const void* wfrag, const float* bias, void* y, double* stats_out,
                           int frames, int T, int H, int W, int Cout, void* stream);
+
+/* Backward of vpt_conv3d_t5_forward w.r.t. its weight and bias (InverseActionNet._conv3d_forward, lib/policy.py:394-403; the input is the uint8
+ * image, so there is no input gradient).  y is the forward's STORED output and supplies the ReLU gate, dy the gradient w.r.t. it (both blocked
+ * [frames][Cout/32][H][W][32]); with g = dy * [y > 0]:
+ *   dw[o][c][dt] += (1/255) sum_{f,p} g[f][p][o] * img[f + dt - 2][p][c]   (a tap outside frame f's own sequence of T frames reads zero),
+ *   db[o]        += sum_{f,p} g[f][p][o]
+ * dw fp32 [Cout][3][5] (the layout of conv3d_layer.layer.weight [Cout,3,5,1,1]), db fp32 [Cout]; both accumulated (caller zeroes).  The products are
+ * exact in fp32; per-workgroup partial sums go to `partials` (VPT_WS_CONV3D_T5_BACKWARD (frames, H, W, -, Cout) bytes) and are added in a fixed
+ * order: no atomics, the same inputs give the same bits.  H*W % 256 == 0, Cout % 32 == 0, Cout <= 128, frames % T == 0. */
+int vpt_conv3d_t5_backward(const uint8_t* img, const void* y, const void* dy, float* dw, float* db, float* partials,
+                           int frames, int T, int H, int W, int Cout, void* stream);
 
 /* The same temporal conv with every output frame ("slot") addressed through an index: slot j is centred on img[src[j]], and tap
  * dt = 0..4 reads img[src[j] + dt - 2] iff lo[j] <= src[j] + dt - 2 < hi[j], zeros otherwise -- the zero padding of
@@ -471,7 +483,8 @@ int vpt_conv_backward_reduce(const void* dacc, const double* gate_u, const doubl
 
 /* vpt_conv_backward_prepare for the layer in front of the max-pool when its forward was vpt_conv3x3_pool_argmax_forward: (dpooled, pooled,
  * pool_mask) [F][Cout/32][H/2][W/2][32] in, dacc [F][Cout/32][H][W][32] and the same sums out.  The ReLU gate is [pooled > 0], the value at
- * the arg-max is the pooled value itself.  H, W: the PRE-pool size (W in {16, 32, 64}).
+ * the arg-max is the pooled value itself.  H, W: the PRE-pool size (W in {16, 32, 64, 128}; 128 -- stack 0 of the
+ * inverse dynamics model -- runs one pooled row per pass).
  * n_gain != NULL: the stack's GroupNorm `n` (lib/impala_cnn.py:118-119) sits between the pool and the incoming gradient and its backward is applied
  * on the fly -- `dpooled` is then G = d loss / d n(pooled), pool_stats [F][2] the frame statistics of pooled and pool_ab [F][2] the sums of
  * vpt_frame_affine_backward's pass 1 (sum G gain, sum G gain xhat): d(pooled) = r (G gain - ab0 / n - xhat ab1 / n) is formed per element with the
@@ -495,8 +508,8 @@ int vpt_conv_first_backward_nfold(const uint8_t* img, const void* wfrag, const v
                                   float* dw, float* db, float* partials, int frames, int H, int W, int Cout, void* stream);
 
 /* Weight gradient of the folded convolution: dw[o][tap][c] += sum_{f,p} dacc[f][o][p] * x[f][c][p + tap] (fp32; caller
- * zeroes or accumulates).  W in {16, 32, 64}.  scratch: fp32 work buffer of vpt_conv3x3_wgrad_scratch_floats() elements
- * (per-frame-group partial sums).  The host maps dw to dW, dgain, dbias (training.py). */
+ * zeroes or accumulates).  W in {16, 32, 64, 128} (128: one LDS buffer instead of two, not tuned).  scratch: fp32 work buffer of vpt_conv3x3_wgrad_scratch_floats() elements
+ * (per-frame-group partial sums).  The host maps dw to dW, dgain, dbias (cnn_training.py). */
 long vpt_conv3x3_wgrad_scratch_floats(int frames, int Cin, int Cout);
 int vpt_conv3x3_wgrad(const void* dacc, const void* x, float* dw, float* scratch, int frames, int H, int W, int Cin, int Cout, void* stream);
 

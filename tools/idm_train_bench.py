@@ -1,5 +1,5 @@
 """One IDM fine-tuning step against one IDM forward on the same batch: how much the trained part (everything behind the frozen CNN) adds.
-python tools/idm_train_bench.py [--batch 8] [--window 128] [--rounds 5] [--model 4x] [--precisions bf16,fp16] [--out idm_train_bench.json]
+python tools/idm_train_bench.py [--batch 8] [--window 128] [--rounds 5] [--model 4x] [--precisions bf16,fp16] [--train-cnn] [--out idm_train_bench.json]
 
 IDMTrainer.step (frozen temporal conv + CNN through the inference path, saving forward of the trunk, ops.idm_loss, the hand-written backward,
 one-launch Adam) and IDMEngine.forward in ONE process per precision, after a warm-up of each, alternating (step, forward, forward, step, ...) so
@@ -34,10 +34,15 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--model", default="4x")
 ap.add_argument("--precisions", default="bf16,fp16")
 ap.add_argument("--profile-steps", type=int, default=0)
+ap.add_argument("--train-cnn", action="store_true")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("idm_train_bench: no GPU (a step time is a GPU measurement; there is no CPU figure)")
+# --train-cnn: the same protocol with IDMTrainer(train_cnn=True).step -- the whole network trained -- alternating with the train_cnn=False step and the two
+# forwards in one process (step_full, step, forward, forward_steady per round); also reported: peak allocated HBM of a full step, and from one extra
+# untimed full step under the op timer the new kernels' own times (ops.conv3d_t5_backward, and the conv wgrad / prepare per layer shape: the 128-wide
+# stack-0 layer is the largest of each).
 
 g = torch.Generator().manual_seed(1)
 img = torch.randint(0, 256, (a.batch, a.window, 128, 128, 3), generator=g, dtype=torch.uint8).to("cuda")
@@ -50,20 +55,30 @@ for prec in a.precisions.split(","):
     pol = pol.to("cuda")
     tr = IDMTrainer(pol, lr=1e-5, weight_decay=0.0)
     run = {"step": lambda: tr.step(img, buttons, camera), "forward": lambda: (pol._ensure_packed(), pol._engine.forward(img))}
+    order = ("step", "forward", "forward_steady")
+    if a.train_cnn:
+        tr_full = IDMTrainer(pol, lr=1e-5, weight_decay=0.0, train_cnn=True)
+        run["stepfull"] = lambda: tr_full.step(img, buttons, camera)
+        order = ("stepfull",) + order
     if a.profile_steps:
         for _ in range(a.profile_steps):
-            run["step"]()
+            run["stepfull" if a.train_cnn else "step"]()
         torch.cuda.synchronize()
         continue
-    for k in ("step", "forward"):          # warm-up: every shape of the timed passes, both paths
+    for k in dict.fromkeys(o.split("_")[0] for o in order):          # warm-up: every shape of the timed passes, every path
+        if k == "stepfull":
+            torch.cuda.reset_peak_memory_stats()
         run[k]()
+        if k == "stepfull":
+            torch.cuda.synchronize()
+            peak_full = torch.cuda.max_memory_allocated()
     torch.cuda.synchronize()
     # a step leaves the packed weights stale and the NEXT call re-packs them (IDMEngine.pack): in the alternation that is the forward right behind
     # the step, so a second forward is timed behind it -- "forward" carries one pack, "forward_steady" none, and a loop of steps pays step + pack
-    ms = {"step": [], "forward": [], "forward_steady": []}
+    ms = {k: [] for k in order}
     with BoxSampler(torch.cuda.current_device()) as box:
         for _ in range(a.rounds):
-            for k in ("step", "forward", "forward_steady"):
+            for k in order:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 run[k.split("_")[0]]()
@@ -81,9 +96,28 @@ for prec in a.precisions.split(","):
                repack_ms=round(pack_ms, 2), step_plus_repack_over_forward_steady=round((med["step"] + pack_ms) / med["forward_steady"], 4),
                forward_spread=round((max(ms["forward"]) - min(ms["forward"])) / med["forward"], 4),
                step_frames_per_s=round(a.batch * a.window / med["step"] * 1e3, 1), steps_taken=tr.step_count, steps_skipped=tr.skipped_steps, box=box.record())
+    if a.train_cnn:
+        from vpt_amd import ops
+        ops.TIMER.reset()
+        ops.TIMER.enabled = True
+        run["stepfull"]()
+        ops.TIMER.enabled = False
+        kern = {k: v for k, v in ops.TIMER.summary().items() if k == "vpt_conv3d_t5_backward"}
+        for pre in ("vpt_conv3x3_wgrad", "vpt_conv_backward_prepare"):
+            kern.update({f"{n} [{w:.4g}]": v for (n, w), v in ops.TIMER.by_shape(pre).items()})
+        ops.TIMER.reset()
+        rec.update(step_full_ms=[round(x, 2) for x in ms["stepfull"]], step_full_ms_median=round(med["stepfull"], 2),
+                   step_full_over_step=round(med["stepfull"] / med["step"], 4), step_full_over_forward_steady=round(med["stepfull"] / med["forward_steady"], 4),
+                   step_full_frames_per_s=round(a.batch * a.window / med["stepfull"] * 1e3, 1), step_full_peak_allocated_gb=round(peak_full / 2 ** 30, 2),
+                   full_trainable_params=int(sum(tr_full.params[n].numel() for n in tr_full.trainable)), full_steps_taken=tr_full.step_count,
+                   full_steps_skipped=tr_full.skipped_steps,
+                   kernels={k: dict(ms=round(v["ms"], 3), calls=v["calls"], gb_s=round(v["bytes"] / v["ms"] * 1e-6, 1) if v["bytes"] else None,
+                                    tf_s=round(v["flops"] / v["ms"] * 1e-9, 1) if v["flops"] else None) for k, v in kern.items()})
     print(json.dumps(rec), flush=True)
     results.append(rec)
     del pol, tr, run
+    if a.train_cnn:
+        del tr_full
     torch.cuda.empty_cache()
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -24,6 +24,7 @@ SIGNATURES = {
     "vpt_conv_first_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vpt_conv3d_t5_forward": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_conv3d_t5_forward_indexed": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vpt_conv3d_t5_backward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_gather_rows": [_P, _P, _P, _L, _L, _I, _P],
     "vpt_idm_decode": [_P] * 9 + [_L, _I, _D, _D, _D, _I, _P],
     "vpt_pack_conv3x3": [_P, _P, _P, _P, _P, _P, _I, _I, _P],

@@ -81,6 +81,7 @@ int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout)
     case VPT_WS_CONV_FIRST_BACKWARD: return 4 * (int64_t)vpt_conv_first_bwd_partial_floats(frames, H, W, Cout);
     case VPT_WS_BC_LOSS: return 4 * (int64_t)vpt_bc_loss_workspace_floats(frames);                          /* (M) */
     case VPT_WS_FULL_ATTENTION_BACKWARD: return 4 * (int64_t)vpt_full_attn_bwd_dkv_floats(frames, H, W);    /* (B, t, hid) */
+    case VPT_WS_CONV3D_T5_BACKWARD: return 4 * (int64_t)vpt_conv3d_bwd_partial_floats(frames, H, W, Cout);
     case VPT_WS_LINEAR_SPLITK: return 4 * (int64_t)frames * H * (int64_t)W;   /* splitk (= frames) x M (= H) x N (= W) fp32 partial slices */
     default: return -1;
   }
@@ -111,6 +112,16 @@ int vpt_conv3d_t5_forward_indexed(const uint8_t* img, const int32_t* src, const 
   a.frames = slots; a.T = 1; a.H = H; a.W = W; a.Cout = Cout; a.NT = (Cout + 127) / 128;
   a.src = src; a.lo = lo; a.hi = hi; a.n_img = img_frames;
   CHECK_LAUNCH(vpt_conv3d_indexed_launch(&a, (hipStream_t)stream), "vpt_conv3d_t5_forward_indexed");
+}
+
+int vpt_conv3d_t5_backward(const uint8_t* img, const void* y, const void* dy, float* dw, float* db, float* partials,
+                           int frames, int T, int H, int W, int Cout, void* stream) {
+  if (!img || !y || !dy || !dw || !db) return fail(-1, "vpt_conv3d_t5_backward: null pointer");
+  if (!partials) return fail(-1, "vpt_conv3d_t5_backward: partials workspace is required");
+  VptConv3dBwdArgs a = {};
+  a.img = img; a.y = (const vpt_op16*)y; a.dy = (const vpt_op16*)dy; a.dw = dw; a.db = db; a.partials = partials;
+  a.frames = frames; a.T = T; a.H = H; a.W = W; a.Cout = Cout; a.accumulate = 1;
+  CHECK_LAUNCH(vpt_conv3d_bwd_launch(&a, (hipStream_t)stream), "vpt_conv3d_t5_backward");
 }
 
 int vpt_conv3x3_forward(const void* x, const void* wpk, const float* edge_sa, const float* edge_sg,

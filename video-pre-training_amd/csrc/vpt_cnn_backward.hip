@@ -575,6 +575,9 @@ __global__ __launch_bounds__(256) void vpt_conv_bwd_prep_anyw_kernel(VptConvBwdP
 //     (1,0): (py,px) 7 + (py+1,px) 1            (1,1): (py,px) 8 + (py,px+1) 6 + (py+1,px) 2 + (py+1,px+1) 0
 // -- positions 0..3 and 6 of a window lie in the blocks of the threads above / to the left.  Rows are processed in passes of 64 / PW pooled
 // rows; a pass's entries go to one of two LDS buffers, the row below the pass's last row comes from the next pass's buffer.
+// W = 128 (PW = 64: stack 0 of the inverse dynamics model) is ONE pooled row per pass: every row below comes from the other buffer -- written by
+// make_entry(p + 1) before the barrier in front of emit_pass(p), overwritten next by make_entry(p + 3), two barriers later -- and a wave holds 16
+// columns of one row, so the ordered edge sums see at most one edge lane per wave.  Nothing but the launcher's width check differs; not tuned.
 struct PoolEntry { u32x4 g; uint32_t codes; };   // gated gradient (8 x 16 bit), arg-max position per channel (8 x 4 bit)
 
 template <bool NFOLD>
@@ -826,7 +829,7 @@ extern "C" int vpt_conv_bwd_prep_launch(const VptConvBwdPrepArgs* a0, hipStream_
   if (a.frames <= 0 || !a.sbuf || !a.coef) return -1;
   if (a.gate_u && (!a.dy || a.res)) return -1;
   if (a.pooled) {      // pool-fused forward with arg-max masks: the pooled-resolution kernel
-    if (a.dy || a.res || !a.dpooled || !a.pool_mask || !a.dacc || a.W < 16 || a.W > 64 || (a.W & (a.W - 1)) || (a.H & 1)) return -1;
+    if (a.dy || a.res || !a.dpooled || !a.pool_mask || !a.dacc || a.W < 16 || a.W > 128 || (a.W & (a.W - 1)) || (a.H & 1)) return -1;
     a.wshift = 31 - __builtin_clz((unsigned)a.W);
     const int PW = a.W >> 1, PH = a.H >> 1, R = 64 / PW;
     if (PH % R) return -1;

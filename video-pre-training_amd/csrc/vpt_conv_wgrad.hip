@@ -17,6 +17,11 @@
 // frame, double-buffered in LDS with the next step's global loads in flight during the MFMAs.  A workgroup
 // sweeps a contiguous range of frames (the grid is one workgroup per CU) and writes its partial sums to scratch;
 // vpt_conv_wgrad_reduce_kernel adds the per-group partials into the fp32 result.
+//
+// W = 128 (stack 0 of the inverse dynamics model: a normed conv on 128 x 128 pixels): one step is one image row, and two buffers of
+// 4 dacc slabs x 130 pixels + 2 x slabs x 3 rows x 128 pixels are 164 864 B, 1 KB over the 160 KB a workgroup can have.  That width runs with
+// ONE buffer: the next step's global loads are issued behind the step's MFMAs and stored after a second barrier (their latency is exposed).
+// Same sums in the same order as the other widths; not tuned (a four-row ring of x rows would fit two buffers).
 #include "vpt_common.h"
 #include "vpt_kernels.h"
 
@@ -40,6 +45,7 @@ __global__ __launch_bounds__(512, 1) void vpt_conv_wgrad_kernel(VptConvWgradArgs
   constexpr int DCB = RB * DP * 64;     // bytes of one cout block's dacc slab
   constexpr int XCB = XR * W * 64;      // bytes of one cin block's x slab
   constexpr int BUF = 4 * DCB + 2 * XCB;
+  constexpr int NBUF = (W == 128) ? 1 : 2;   // LDS buffers (file comment)
   constexpr int NXC = 2 * XR * W * 4;   // 16-byte x chunks per step
   constexpr int NX = (NXC + 511) / 512;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -56,7 +62,7 @@ __global__ __launch_bounds__(512, 1) void vpt_conv_wgrad_kernel(VptConvWgradArgs
   const int f0 = grp * a.frames_per_wg, f1 = min(f0 + a.frames_per_wg, a.frames);
 
   // dacc halo columns of both buffers: zero once, never overwritten
-  for (int i = tid; i < 2 * 4 * RB * 2 * 4; i += 512) {
+  for (int i = tid; i < NBUF * 4 * RB * 2 * 4; i += 512) {
     int q = i;
     const int part = q & 3; q >>= 2;
     const int side = q & 1; q >>= 1;
@@ -170,8 +176,8 @@ __global__ __launch_bounds__(512, 1) void vpt_conv_wgrad_kernel(VptConvWgradArgs
   }
   __syncthreads();
   for (int s = 0; s < nsteps; ++s) {
-    load_step(min(s + 1, nsteps - 1));   // the last iteration re-stages its own step into the idle buffer (harmless)
-    const unsigned char* base = smem + (s & 1) * BUF;
+    if constexpr (NBUF == 2) load_step(min(s + 1, nsteps - 1));   // the last iteration re-stages its own step into the idle buffer (harmless)
+    const unsigned char* base = smem + (NBUF == 2 ? (s & 1) : 0) * BUF;
     const unsigned char* dA = base + wo * DCB + lane_off;
     const unsigned char* xB = base + 4 * DCB + wi * XCB + lane_off;
     // Two fragment register sets: while the nine MFMAs of 16-pixel slice ks issue, the six fragments of slice ks + 1 are
@@ -212,7 +218,13 @@ __global__ __launch_bounds__(512, 1) void vpt_conv_wgrad_kernel(VptConvWgradArgs
 #undef WG_LDA
 #undef WG_LDB
 #undef WG_SB
-    store_step((s + 1) & 1);
+    if constexpr (NBUF == 2) {
+      store_step((s + 1) & 1);
+    } else {
+      load_step(min(s + 1, nsteps - 1)); // issued behind the MFMAs: held across them, the 40 staging registers of this width spill
+      __syncthreads();                   // every wave has read this step's fragments
+      store_step(0);
+    }
     __syncthreads();
   }
 
@@ -250,20 +262,22 @@ extern "C" int vpt_conv_wgrad_groups(int frames, int Cin, int Cout) {
 
 extern "C" int vpt_conv_wgrad_launch(const VptConvWgradArgs* a_in, hipStream_t stream) {
   VptConvWgradArgs a = *a_in;
-  if ((a.Cin & 31) || (a.Cout & 31) || a.frames <= 0 || (a.W != 16 && a.W != 32 && a.W != 64) || (a.H % (VPT_WGRAD_PXS / a.W)) || !a.partial) return -1;
+  if ((a.Cin & 31) || (a.Cout & 31) || a.frames <= 0 || (a.W != 16 && a.W != 32 && a.W != 64 && a.W != 128) || (a.H % (VPT_WGRAD_PXS / a.W)) || !a.partial) return -1;
   a.OT = (a.Cout + 127) / 128;
   const int tiles = a.OT * (((a.Cin >> 5) + 1) >> 1);
   const int groups = vpt_conv_wgrad_groups(a.frames, a.Cin, a.Cout);
   a.frames_per_wg = (a.frames + groups - 1) / groups;
   const int RB = VPT_WGRAD_PXS / a.W;
-  const size_t lds = 2 * (size_t)(4 * RB * (a.W + 2) * 64 + 2 * (RB + 2) * a.W * 64);
-  static unsigned long long optin_done[3] = {0, 0, 0};
+  const size_t lds = (a.W == 128 ? 1 : 2) * (size_t)(4 * RB * (a.W + 2) * 64 + 2 * (RB + 2) * a.W * 64);
+  static unsigned long long optin_done[4] = {0, 0, 0, 0};
   if (!vpt_lds_optin((const void*)vpt_conv_wgrad_kernel<64>, 160 * 1024, &optin_done[0]) ||
       !vpt_lds_optin((const void*)vpt_conv_wgrad_kernel<32>, 160 * 1024, &optin_done[1]) ||
-      !vpt_lds_optin((const void*)vpt_conv_wgrad_kernel<16>, 160 * 1024, &optin_done[2]))
+      !vpt_lds_optin((const void*)vpt_conv_wgrad_kernel<16>, 160 * 1024, &optin_done[2]) ||
+      !vpt_lds_optin((const void*)vpt_conv_wgrad_kernel<128>, 160 * 1024, &optin_done[3]))
     return -4;
   const dim3 grid((unsigned)(tiles * groups));
-  if (a.W == 64) hipLaunchKernelGGL(vpt_conv_wgrad_kernel<64>, grid, dim3(512), lds, stream, a);
+  if (a.W == 128) hipLaunchKernelGGL(vpt_conv_wgrad_kernel<128>, grid, dim3(512), lds, stream, a);
+  else if (a.W == 64) hipLaunchKernelGGL(vpt_conv_wgrad_kernel<64>, grid, dim3(512), lds, stream, a);
   else if (a.W == 32) hipLaunchKernelGGL(vpt_conv_wgrad_kernel<32>, grid, dim3(512), lds, stream, a);
   else hipLaunchKernelGGL(vpt_conv_wgrad_kernel<16>, grid, dim3(512), lds, stream, a);
   const int n4 = a.Cout * 9 * a.Cin / 4;

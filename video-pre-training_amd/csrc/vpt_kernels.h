@@ -119,6 +119,17 @@ struct VptConv3dArgs {
   int n_img;
 };
 
+struct VptConv3dBwdArgs {
+  const uint8_t* img;      // [B*T][H][W][3]
+  const vpt_op16* y;       // [B*T][Cout/32][H][W][32]  the forward's stored output (the ReLU gate is [y > 0])
+  const vpt_op16* dy;      // [B*T][Cout/32][H][W][32]  gradient w.r.t. y
+  float* dw;               // [Cout][3][5]
+  float* db;               // [Cout]
+  float* partials;         // vpt_conv3d_bwd_partial_floats(): one slab row [Cout*15 | Cout] per workgroup, then vpt_slab_sum's scratch
+  int frames, T, H, W, Cout, accumulate;
+  int items_per_wg;        // set by the launcher: (frame, 256-pixel chunk) items per workgroup
+};
+
 struct VptPoolArgs {
   const vpt_op16* x;       // [F][CB][H][W][32]  (non-negative values: post-ReLU)
   vpt_op16* y;             // [F][CB][H/2][W/2][32]
@@ -477,6 +488,8 @@ int vpt_nfold_coef_launch(const VptNfoldCoefArgs* a, hipStream_t s);
 int vpt_conv_first_launch(const VptConvFirstArgs* a, hipStream_t s);
 int vpt_conv3d_launch(const VptConv3dArgs* a, hipStream_t s);
 int vpt_conv3d_indexed_launch(const VptConv3dArgs* a, hipStream_t s);
+long vpt_conv3d_bwd_partial_floats(int frames, int H, int W, int Cout);
+int vpt_conv3d_bwd_launch(const VptConv3dBwdArgs* a, hipStream_t s);
 int vpt_gather_rows_launch(const float* x, const int32_t* index, float* y, long rows_in, long n, int D, hipStream_t s);
 int vpt_idm_decode_launch(const float* lp_buttons, const float* lp_camera, int64_t* buttons, int64_t* camera, float* log_prob, int64_t* joint_buttons,
                           int64_t* joint_camera, double* camera_deg, uint8_t* null_flag, long n, int n_camera_bins, double maxval, double binsize, double mu,

@@ -1,15 +1,19 @@
-"""Fine-tuning of the inverse-dynamics model on MI355X: everything BEHIND the CNN.
+"""Training of the inverse-dynamics model on MI355X: everything behind the CNN (the default), or the whole network from the pixels (train_cnn=True).
 
 The IDM (lib/policy.py:342-467) is temporal Conv3d -> IMPALA CNN -> 256 -> hid linear -> transformer blocks with mask "none" -> ReLU -> final_ln ->
-20 two-way button groups + 2 eleven-way camera groups.  About 99 % of its forward FLOPs are the per-frame CNN; that part stays frozen here and runs
-through the inference path with nothing saved.  The trained part -- ImgObsProcess.linear, the transformer blocks, final_ln and the two heads --
+20 two-way button groups + 2 eleven-way camera groups.  About 99 % of its forward FLOPs are the per-frame CNN; by default that part stays frozen and runs
+through the inference path with nothing saved.  The part that is always trained -- ImgObsProcess.linear, the transformer blocks, final_ln and the two heads --
 holds all of the window-level reasoning.
 
     loss = sum_frames w (nll_buttons + nll_camera) / sum_frames w,   nll_* = -sum over the head's groups of log pi(label)
            (the negative of pi_head.logprob, lib/action_head.py:176-184,252-253, averaged over frames)
 
-NOT built: the gradients of the temporal conv (`net.conv3d_layer.*`) and of the CNN (`net.img_process.cnn.*`, the dense layer included) -- those
-tensors are frozen, as under BCTrainer(train_cnn=False) --, data-parallel IDM steps, and an autograd boundary for the IDM.
+train_cnn=True is the first stage of the VPT method, training the IDM itself: the temporal conv (`net.conv3d_layer.*`) and the IMPALA CNN
+(`net.img_process.cnn.*`, the dense layer included) get gradients too.  The CNN's saving forward and its backward are BCTrainer's own
+(cnn_training.CnnTrainingMixin, one copy of the launch order) with stack 0 fed by the temporal conv's output: there `firstconv` is a normed 3x3 conv on
+128 x 128 pixels, its dgrad returns dx0, and ops.conv3d_t5_backward turns (image, x0, dx0) into the temporal conv's weight and bias gradient.
+
+NOT built: data-parallel IDM steps, an autograd boundary for the IDM, and chunk streams for the CNN backward (one stream).
 
 The backward runs on the HIP kernels of the BC step (training.linear_backward, ops.layernorm_backward, ops.gate_cast, ops.column_sum_,
 ops.adam_step_multi_) plus two of its own: ops.full_attention_backward (the mask-"none" attention) and ops.idm_loss (the grouped heads' loss,
@@ -19,25 +23,34 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
-from .engine import action_heads
+from .cnn_training import CnnTrainingMixin
+from .engine import DENSE_SPLITK, action_heads
 from .training import BCTrainer, linear_backward
 
 _FROZEN = ("net.conv3d_layer.", "net.img_process.cnn.")
 _UNREACHED = ("net.lastlayer.",)       # computed and discarded by the reference (lib/policy.py:390-391): not part of the function that is trained
 
 
-class IDMTrainer:
+class IDMTrainer(CnnTrainingMixin):
+    stack0_from_x0 = True        # the CNN's stack 0 is fed by the temporal conv (cnn_training.py)
+    dense_tiling = "throughput"  # as IDMEngine: the MFMA GEMM whatever the row count (a one-window chunk of <= 8 frames would take the GEMV kernel)
+
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
-                 optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200):
+                 optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200, train_cnn: bool = False):
         """policy: lib.policy.InverseActionPolicy on the GPU.  Trainable: `net.img_process.linear.*`, `net.pre_lstm_ln.*` (when configured), every
-        `net.recurrent_layer.blocks.*` tensor, `net.final_ln.*`, `pi_head.buttons.*`, `pi_head.camera.*`.  Frozen: `net.conv3d_layer.*` and every
-        `net.img_process.cnn.*` tensor (the dense layer included) -- the gradients of the temporal conv and of the CNN are not built, so there is no
-        `train_cnn` argument.  (`r_layer.*` of a block is trainable by name but unreached -- mask "none" has no relative-position bias -- so its
+        `net.recurrent_layer.blocks.*` tensor, `net.final_ln.*`, `pi_head.buttons.*`, `pi_head.camera.*`.  train_cnn=False (default) freezes
+        `net.conv3d_layer.*` and every `net.img_process.cnn.*` tensor (the dense layer included) and launches what it always launched.
+        train_cnn=True trains those 49 tensors as well: per chunk of whole windows (the engine's cnn_chunk granularity) ops.conv3d_t5 with x0 kept, the
+        saving CNN forward, the dense layer; backward per chunk dense -> stacks 2, 1, 0 -> dx0 -> ops.conv3d_t5_backward, on one stream.  It needs the
+        pool-fused forward (VPT_BC_FUSED_POOL=0 raises).  The saving forward does not use the inference path's `n` and dense folds, so with
+        train_cnn=True the log-probs equal IDMEngine.forward's to the parity bounds, not bit for bit (BCTrainer(train_cnn=True) has the same property);
+        about 27 MB of activations per frame are kept on the 4x model.  (`r_layer.*` of a block is trainable by name but unreached -- mask "none" has no relative-position bias -- so its
         gradient is exact zeros and only weight decay moves it, as torch.optim.Adam would; `b_nd` is [10, 0]: nothing to train; `net.lastlayer.*`
         is computed and discarded by the reference and takes no part.)
         optimizer_state=False: gradients only, no Adam moments.  The fp16 mode uses BCTrainer's loss scaling unchanged (see there): `loss_scale`
         defaults to 256 (1 = off in bf16), the loss gradient is written as loss_scale / temperature x (softmax - one-hot) per frame, the optimiser
         launch un-scales, an overflowed step is skipped on the device, the scale halves then and doubles after `scale_growth_interval` clean steps."""
+        self.train_cnn = bool(train_cnn)
         self.policy = policy
         self.engine = policy._engine
         self.dtype = self.engine.dtype
@@ -46,13 +59,17 @@ class IDMTrainer:
         self.scale_growth_interval, self._clean_steps, self.skipped_steps = int(scale_growth_interval), 0, 0
         self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
         self.step_count = 0
+        self._cnn_flags_from_env()
+        if self.train_cnn and not self.fused_pool:
+            raise RuntimeError("IDMTrainer(train_cnn=True) needs the pool-fused forward (ops.conv3x3_pool_argmax): at 128 x 128 only the pooled entry of "
+                               "the conv backward is built -- unset VPT_BC_FUSED_POOL=0")
         self.params: Dict[str, torch.nn.Parameter] = dict(policy.named_parameters())
         self.trainable = [n for n in self.params if self._is_trainable(n)]
         self.m = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
         self.v = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
 
     def _is_trainable(self, name: str) -> bool:
-        if name.startswith(_FROZEN) or name.startswith(_UNREACHED):
+        if (name.startswith(_FROZEN) and not self.train_cnn) or name.startswith(_UNREACHED):
             return False
         return self.params[name].numel() > 0            # (b_nd is [10, maxlen = 0])
 
@@ -60,7 +77,7 @@ class IDMTrainer:
     def state_dict(self) -> dict:
         self._need_optimizer_state()
         return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
-                    loss_scale=self.loss_scale, train_cnn=False, exp_avg={n: t.detach().clone() for n, t in self.m.items()},
+                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, exp_avg={n: t.detach().clone() for n, t in self.m.items()},
                     exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
 
     def _need_optimizer_state(self):
@@ -136,7 +153,9 @@ class IDMTrainer:
         """IDMEngine.forward with what the backward needs kept from the dense layer's pre-activation output `d` (fp32 [M, 256]) onward.  The frozen
         part in front of it runs exactly as the engine runs it (ops.conv3d_t5 per whole window, the CNN + dense layer in cnn_chunk pieces, nothing
         kept); behind it the same launches with the same tilings and split-K choice (the engine's, never the row count's), so the log-probs
-        S["lp_b"] [M, 20, 2] / S["lp_c"] [M, 2, 11] equal IDMEngine.forward's bit for bit."""
+        S["lp_b"] [M, 20, 2] / S["lp_c"] [M, 2, 11] equal IDMEngine.forward's bit for bit.
+        train_cnn=True: the same chunks through the saving CNN forward (x0 and every CNN activation kept in S["cnn_saved"]; no `n` / dense folds, so
+        the log-probs equal the engine's to the parity bounds only)."""
         pol, eng = self.policy, self.engine
         pol._ensure_packed()
         cfg, w = eng.cfg, eng.w
@@ -148,13 +167,20 @@ class IDMTrainer:
         sk, dt, tl = eng.linear_splitk, self.dtype, "throughput"
         frames = img_u8.reshape(m, *img_u8.shape[2:]).contiguous()
         wfrag, bias = w["conv3d"]
-        outs = []
+        outs, cnn_saved = [], []
         step = max(1, eng.cnn_chunk // t) * t if t <= eng.cnn_chunk else t
         for i in range(0, m, step):
             fr = frames[i:i + step]
             s0 = torch.zeros(fr.shape[0], 2, dtype=torch.float64, device=fr.device)
             x0 = ops.conv3d_t5(fr, wfrag, bias, eng.c3d_out, t, stats_out=s0)
-            outs.append(eng._cnn_dense(None, x0=x0, s_x0=s0))
+            if self.train_cnn:
+                xn, sv = self._cnn_forward_saving(fr, x0=x0, s_x0=s0)
+                cnn_saved.append(sv)
+                d32, _ = ops.linear(xn.view(xn.shape[0], -1), w["net.img_process.cnn.dense.w"], 256, splitk=DENSE_SPLITK, tiling=self.dense_tiling)
+                outs.append(d32)
+                del xn
+            else:
+                outs.append(eng._cnn_dense(None, x0=x0, s_x0=s0))
             del x0
         d = outs[0] if len(outs) == 1 else torch.cat(outs, 0)                        # [M, 256] pre-ReLU dense output: a constant of the backward
         pl = "net.img_process.linear."
@@ -183,13 +209,15 @@ class IDMTrainer:
             z, _ = ops.linear(lb, w[h + ".w"], groups * n, bias=w[h + ".b"], tiling=tl, splitk=sk)
             lps[h] = action_heads(z, ((h, 0, groups, n),), bsz, t, cfg["temperature"])[h].view(m, groups, n)
         return dict(m=m, bsz=bsz, t=t, dev=img_u8.device, d=d, dn=dn, x_lin16=x_lin16, x_pre=x_pre, saved=saved, x_trunk=x_trunk, lb=lb,
-                    lp_b=lps["buttons"], lp_c=lps["camera"])
+                    lp_b=lps["buttons"], lp_c=lps["camera"], cnn_saved=cnn_saved, cnn_step=step)
 
     @torch.no_grad()
     def backward_from(self, S: dict, dz: torch.Tensor) -> Dict[str, torch.Tensor]:
         """dz: 16-bit [M, 64] = d loss / d (the two heads' logits, buttons first) -> the gradient of every trainable tensor.  Launch order: heads
         (dgrad, wgrad, bias sums) -> final_ln through its ReLU -> per block, last to first: mlp1, mlp0, its LayerNorm (+ skip), proj,
-        ops.full_attention_backward, the fused QKV GEMM (+ skip), pre_r_ln -> pre_lstm_ln -> ImgObsProcess.linear and its LayerNorm."""
+        ops.full_attention_backward, the fused QKV GEMM (+ skip), pre_r_ln -> pre_lstm_ln -> ImgObsProcess.linear and its LayerNorm; with
+        train_cnn=True then per chunk of S["cnn_saved"] (released chunk by chunk): dense -> stacks 2, 1, 0 -> dx0 -> ops.conv3d_t5_backward, and the
+        CNN's finish step."""
         eng = self.engine
         cfg = eng.cfg
         P = {n: p.detach() for n, p in self.params.items()}
@@ -248,12 +276,24 @@ class IDMTrainer:
         if cfg["use_pre_lstm_ln"]:
             g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"] = zeros(hid), zeros(hid)
             dx = ops.layernorm_backward(S["x_pre"], P["net.pre_lstm_ln.weight"], dx, g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"])
-        # ImgObsProcess.linear: x = relu(dn Wlin^T); its LayerNorm sits on relu(d), d being the frozen CNN's output (its gradient is dropped)
+        # ImgObsProcess.linear: x = relu(dn Wlin^T); its LayerNorm sits on relu(d), d being the CNN's output (its gradient goes on only with train_cnn)
         pl = "net.img_process.linear."
         dx16 = ops.gate_cast(dx, hid, mask=S["x_lin16"])
         ddn, _, g[pl + "layer.weight"] = linear_backward(dx16, hid, S["dn"], P[pl + "layer.weight"])
         g[pl + "norm.weight"], g[pl + "norm.bias"] = zeros(256), zeros(256)
-        ops.layernorm_backward(S["d"], P[pl + "norm.weight"], ddn, g[pl + "norm.weight"], g[pl + "norm.bias"], relu_in=True)
+        dd = ops.layernorm_backward(S["d"], P[pl + "norm.weight"], ddn, g[pl + "norm.weight"], g[pl + "norm.bias"], relu_in=True)
+        if self.train_cnn:
+            cnn_saved, step = S["cnn_saved"], S["cnn_step"]
+            acc = self._cnn_backward_begin(P)
+            c3d = (torch.zeros_like(P["net.conv3d_layer.layer.weight"], dtype=torch.float32), torch.zeros_like(P["net.conv3d_layer.layer.bias"], dtype=torch.float32))
+            for ci, i in enumerate(range(0, m, step)):
+                sv = cnn_saved[ci]
+                dx0 = self._cnn_backward_chunk(sv, dd[i:i + step].contiguous(), acc)
+                ops.conv3d_t5_backward(sv["img"], sv["stacks"][0]["x_prev"], dx0, t, out=c3d)
+                cnn_saved[ci] = None
+                del sv, dx0
+            self._cnn_backward_finish(acc, P, g)
+            g["net.conv3d_layer.layer.weight"], g["net.conv3d_layer.layer.bias"] = c3d
         return g
 
     @torch.no_grad()

@@ -71,7 +71,7 @@ def _call(name, meta, *args, fmt="bf16", label=None):
 
 WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
 WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
-WS_FULL_ATTENTION_BACKWARD = 11
+WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD = 11, 12
 FULL_ATTENTION_MAX_T = 160      # the mask="none" attention kernels' longest window (forward and backward)
 
 
@@ -503,6 +503,30 @@ def conv3d_t5(img_u8, wfrag, bias, cout, t, stats_out=None):
     _call("vpt_conv3d_t5_forward", dict(flops=2.0 * f * h * w * cout * 15, bytes=f * h * w * (3 + 2 * cout)),
           ptr(img_u8), ptr(wfrag), ptr(bias), ptr(y), ptr(stats_out), f, t, h, w, cout, _stream(), fmt=fmt)
     return y
+
+
+def conv3d_t5_backward(img_u8, y, dy, t, out=None):
+    """Weight and bias gradient of conv3d_t5: img_u8 [F = B*t, H, W, 3] uint8, y the forward's stored output (its ReLU gate is [y > 0]) and dy the
+    gradient w.r.t. it, both blocked [F, cout/32, H, W, 32] -> (dW fp32 [cout, 3, 5, 1, 1], db fp32 [cout]); accumulated into out=(dW, db) when given.
+    A tap never crosses the edge of a frame's own window of t frames.  Bit-reproducible (fixed-order sums, no atomics)."""
+    _chk(img_u8, torch.uint8, "img"); _chk(y, OP16, "y"); _chk(dy, OP16, "dy")
+    f, h, w, c3 = img_u8.shape
+    if c3 != 3 or y.dim() != 5 or y.shape[0] != f or tuple(y.shape[2:]) != (h, w, 32) or dy.shape != y.shape:
+        raise ValueError(f"conv3d_t5_backward: img {tuple(img_u8.shape)}, y {tuple(y.shape)} and dy {tuple(dy.shape)} do not belong together")
+    cout = y.shape[1] * 32
+    if t <= 0 or f % t or (h * w) % 256 or cout > 128:
+        raise ValueError(f"conv3d_t5_backward: needs frames % t == 0, H * W % 256 == 0 and cout <= 128, got frames {f}, t {t}, {h} x {w}, cout {cout}")
+    fmt = _fmt(y, dy)[1]
+    if out is None:
+        out = (torch.zeros(cout, 3, 5, 1, 1, dtype=torch.float32, device=y.device), torch.zeros(cout, dtype=torch.float32, device=y.device))
+    dw, db = out
+    _chk(dw, torch.float32, "dw"); _chk(db, torch.float32, "db")
+    if dw.numel() != cout * 15 or db.numel() != cout:
+        raise ValueError(f"conv3d_t5_backward: out must be ([{cout}, 3, 5, 1, 1], [{cout}]), got {tuple(dw.shape)}, {tuple(db.shape)}")
+    part = _workspace(WS_CONV3D_T5_BACKWARD, f, h, w, 0, cout, device=y.device, fmt=fmt)
+    _call("vpt_conv3d_t5_backward", dict(flops=2.0 * f * h * w * cout * 16, bytes=f * h * w * (15 + 4 * cout)),
+          ptr(img_u8), ptr(y), ptr(dy), ptr(dw), ptr(db), ptr(part), f, t, h, w, cout, _stream(), fmt=fmt)
+    return dw, db
 
 
 def conv3d_t5_indexed(img_u8, src, lo, hi, wfrag, bias, cout, stats_out=None):
