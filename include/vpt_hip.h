@@ -83,10 +83,11 @@ int vpt_chw_to_blocked(const float* src, float* dst, int64_t rows, int C, int H,
  *   VPT_WS_BC_LOSS               (M, -, -, -, -)             vpt_bc_loss's / vpt_idm_loss's workspace (the record slab + its reduction scratch)
  *   VPT_WS_FULL_ATTENTION_BACKWARD (B, t, hid, -, -)         vpt_full_attention_backward's dkv_slab (one slot per 32-query tile)
  *   VPT_WS_CONV3D_T5_BACKWARD    (frames, H, W, -, Cout)     vpt_conv3d_t5_backward's partials (one slab row per workgroup + the reduction's scratch)
+ *   VPT_WS_RL_LOSS               (M, -, -, -, -)             vpt_rl_loss's workspace (the [M][16] record slab + its reduction scratch)
  * Returns -1 for an unknown op. */
 enum { VPT_WS_CONV3X3_WGRAD = 1, VPT_WS_CONV_BACKWARD_PREPARE = 2, VPT_WS_LINEAR_SPLITK = 3, VPT_WS_LAYERNORM_BACKWARD = 4, VPT_WS_COLUMN_SUM = 5,
        VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9,
-       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11, VPT_WS_CONV3D_T5_BACKWARD = 12 };
+       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11, VPT_WS_CONV3D_T5_BACKWARD = 12, VPT_WS_RL_LOSS = 13 };
 int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout);
 int vpt_pack_conv3x3(const float* weight, const float* gain, const float* bias, void* wpk, float* edge_sa, float* edge_sg,
                      int Cout, int Cin, void* stream);
@@ -445,6 +446,41 @@ int vpt_full_attention_backward(const float* qkv, const float* dout, float* dqkv
 int vpt_idm_loss(const float* lp_buttons, const float* lp_camera, const int64_t* act_buttons, const int64_t* act_camera,
                  const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
                  int M, int gb, int nb, int gc, int nc, int ldz, float scale, void* stream);
+
+/* ---- reinforcement-learning fine-tuning of the cloned policy (the third stage of the method; the reference ships no RL training script, only the
+ * pieces such a loss is made of: the heads' logprob / entropy / kl_divergence, lib/action_head.py:176-203,252-275, and the value head) ---- */
+
+/* Clipped policy gradient + KL to a frozen prior + entropy bonus + value loss, their gradient w.r.t. the fused head logits and their metrics in one
+ * launch.  With l, q the log-probs of the policy and of the prior, p = exp(l), per head K = sum p (l - q), H = -sum p l (a term with p = 0 counts 0):
+ *   lp = l_b[a_b] + l_c[a_c]  (lib/action_head.py:252-253 sums the heads),  rho = expf(lp - old_log_prob),  t^ = (value_target - mean) / std,
+ *   L_r = -min(rho A, clamp(rho, 1 - clip, 1 + clip) A) + kl_coef (K_b + K_c) - entropy_coef (H_b + H_c) + value_coef (v - t^)^2,
+ *   loss = sum_rows w L / sum_rows w.
+ * The KL is KL(pi || prior): the expectation runs over the CURRENT policy (lib/action_head.py:198-203, kl_divergence(pi, prior)).  The value term is
+ * lib/scaled_mse_head.py:37-43: `value` is the raw head output (normalised space, element r at value[r * value_stride] -- the value column of the
+ * fused head logits), value_target the denormalised return, vnorm a DEVICE pair (mean, std) of the normaliser (lib/normalize_ewma.py:27-31,55).
+ * prior_buttons / prior_camera may both be NULL (no KL term, K = 0), value may be NULL (no value term; value_target and vnorm are then not read),
+ * weight may be NULL (all ones).  A coefficient of 0 skips its term.  Every output is optional (NULL):
+ *   dz        16-bit [M][ldz], ldz >= nb + nc + 1:  rs [ c (onehot - p) + kl_coef p ((l - q) - K) + entropy_coef p (l + H) ] / temperature per head with
+ *             c = -A rho, or 0 where (A > 0 and rho > 1 + clip) or (A < 0 and rho < 1 - clip) (the gradient of torch.min / clamp), rs = scale weight[row];
+ *             column nb + nc: rs 2 value_coef (v - t^); further columns zero.  The caller folds 1 / sum w (and the fp16 loss scale) into `scale`.
+ *   frame_out fp32 [M][16]: the surrogate -min(.), K_b, K_c, H_b, H_c, (v - t^)^2, rho, clipped (1 where c was zeroed), lp, old_log_prob - lp, w,
+ *             1 if w > 0, then four zeros -- the frame's own, unweighted values;
+ *   totals    fp32 [16]: sum_rows w frame_out[row][k] for k < 10, sum w, the number of rows with w > 0, zeros; added in a fixed order through `workspace`
+ *             (vpt_workspace_bytes(VPT_WS_RL_LOSS, M, ...) bytes, required with totals; M <= 65536): no atomics, the same inputs give the same bits.
+ * A row with weight 0 stores exact zeros in dz and adds exact zeros to totals whatever its inputs hold (NaN included); actions are only compared with
+ * column indices.  With kl_coef = entropy_coef = value_coef = 0, A = 1 and rho = 1 the policy columns of dz are vpt_bc_loss's at scale / temperature. */
+int vpt_rl_loss(const float* lp_buttons, const float* lp_camera, const float* prior_buttons, const float* prior_camera,
+                const int64_t* act_buttons, const int64_t* act_camera, const float* old_log_prob, const float* advantage,
+                const float* value, int64_t value_stride, const float* value_target, const float* vnorm, const float* weight,
+                void* dz, float* frame_out, float* totals, float* workspace, int M, int nb, int nc, int ldz,
+                float clip, float kl_coef, float entropy_coef, float value_coef, float temperature, float scale, void* stream);
+
+/* Generalised advantage estimation over [B][T] rollouts (reward, value fp32; first uint8: frame t starts an episode; last_value [B] and next_first [B]
+ * describe the frame after the rollout; `value` and `ret` are denormalised, lib/scaled_mse_head.py:45-47):
+ *   nt = !first[t+1] (t = T-1: !next_first),  delta = r + (nt ? gamma V_{t+1} : 0) - V,  adv = delta + (nt ? (gamma lambda) adv_{t+1} : 0),  ret = adv + V,
+ * one lane per sequence walking back over t, in this order of fp32 operations without contraction: a float32 host loop reproduces it bit for bit. */
+int vpt_gae(const float* reward, const float* value, const uint8_t* first, const float* last_value, const uint8_t* next_first,
+            float* adv, float* ret, int B, int T, float gamma, float lam, void* stream);
 
 /* ---- backward of the IMPALA CNN (behavioural_cloning.py:117-119 obtains these from torch autograd) ---- */
 

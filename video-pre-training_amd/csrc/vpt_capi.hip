@@ -82,6 +82,7 @@ int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout)
     case VPT_WS_BC_LOSS: return 4 * (int64_t)vpt_bc_loss_workspace_floats(frames);                          /* (M) */
     case VPT_WS_FULL_ATTENTION_BACKWARD: return 4 * (int64_t)vpt_full_attn_bwd_dkv_floats(frames, H, W);    /* (B, t, hid) */
     case VPT_WS_CONV3D_T5_BACKWARD: return 4 * (int64_t)vpt_conv3d_bwd_partial_floats(frames, H, W, Cout);
+    case VPT_WS_RL_LOSS: return 4 * (int64_t)vpt_rl_loss_workspace_floats(frames);                          /* (M) */
     case VPT_WS_LINEAR_SPLITK: return 4 * (int64_t)frames * H * (int64_t)W;   /* splitk (= frames) x M (= H) x N (= W) fp32 partial slices */
     default: return -1;
   }
@@ -575,6 +576,41 @@ int vpt_idm_loss(const float* lp_buttons, const float* lp_camera, const int64_t*
   a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.act_buttons = (const long*)act_buttons; a.act_camera = (const long*)act_camera;
   a.weight = weight; a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.gb = gb; a.nb = nb; a.gc = gc; a.nc = nc; a.ldz = ldz; a.scale = scale;
   CHECK_LAUNCH(vpt_idm_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_idm_loss");
+}
+
+int vpt_rl_loss(const float* lp_buttons, const float* lp_camera, const float* prior_buttons, const float* prior_camera,
+                const int64_t* act_buttons, const int64_t* act_camera, const float* old_log_prob, const float* advantage,
+                const float* value, int64_t value_stride, const float* value_target, const float* vnorm, const float* weight,
+                void* dz, float* frame_out, float* totals, float* workspace, int M, int nb, int nc, int ldz,
+                float clip, float kl_coef, float entropy_coef, float value_coef, float temperature, float scale, void* stream) {
+  if (!lp_buttons || !lp_camera || !act_buttons || !act_camera) return fail(-1, "vpt_rl_loss: null log-probs / actions");
+  if (!old_log_prob || !advantage) return fail(-1, "vpt_rl_loss: null old_log_prob / advantage");
+  if (M <= 0 || nb <= 0 || nc <= 0) return fail(-1, "vpt_rl_loss: M and the head widths must be positive");
+  if ((prior_buttons == nullptr) != (prior_camera == nullptr)) return fail(-1, "vpt_rl_loss: give both priors or neither");
+  if (value && (!value_target || !vnorm)) return fail(-1, "vpt_rl_loss: the value term needs value_target and vnorm");
+  if (value && value_stride < 1) return fail(-1, "vpt_rl_loss: value_stride must be positive");
+  if (dz && ldz < nb + nc + 1) return fail(-1, "vpt_rl_loss: ldz < nb + nc + 1");
+  if (!(temperature > 0.f)) return fail(-1, "vpt_rl_loss: temperature must be positive");
+  if (!(clip >= 0.f)) return fail(-1, "vpt_rl_loss: clip must be non-negative");
+  if (totals && !workspace) return fail(-1, "vpt_rl_loss: totals need the workspace (VPT_WS_RL_LOSS)");
+  if (totals && M > 65536) return fail(-2, "vpt_rl_loss: totals of at most 65536 rows");
+  VptRlLossArgs a = {};
+  a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.prior_buttons = prior_buttons; a.prior_camera = prior_camera;
+  a.act_buttons = (const long*)act_buttons; a.act_camera = (const long*)act_camera; a.old_log_prob = old_log_prob; a.advantage = advantage;
+  a.value = value; a.value_stride = (long)value_stride; a.value_target = value_target; a.vnorm = vnorm; a.weight = weight;
+  a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz;
+  a.clip = clip; a.kl_coef = kl_coef; a.entropy_coef = entropy_coef; a.value_coef = value_coef; a.inv_temp = 1.0f / temperature; a.scale = scale;
+  CHECK_LAUNCH(vpt_rl_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_rl_loss");
+}
+
+int vpt_gae(const float* reward, const float* value, const uint8_t* first, const float* last_value, const uint8_t* next_first,
+            float* adv, float* ret, int B, int T, float gamma, float lam, void* stream) {
+  if (!reward || !value || !first || !last_value || !next_first || !adv || !ret) return fail(-1, "vpt_gae: null pointer");
+  if (B <= 0 || T <= 0) return fail(-1, "vpt_gae: B and T must be positive");
+  VptGaeArgs a = {};
+  a.reward = reward; a.value = value; a.first = first; a.last_value = last_value; a.next_first = next_first; a.adv = adv; a.ret = ret;
+  a.B = B; a.T = T; a.gamma = gamma; a.lam = lam;
+  CHECK_LAUNCH(vpt_gae_launch(&a, (hipStream_t)stream), "vpt_gae");
 }
 
 int vpt_full_attention_backward(const float* qkv, const float* dout, float* dqkv, float* dkv_slab,

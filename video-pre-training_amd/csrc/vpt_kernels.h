@@ -337,6 +337,39 @@ struct VptIdmLossArgs {     // IDM loss over gb + gc independent categorical gro
   float scale;
 };
 
+struct VptRlLossArgs {      // clipped policy gradient + KL(pi || prior) + entropy bonus + value loss of a frame (vpt_rl_loss_kernel, vpt_rl.hip)
+  const float* lp_buttons; // [M][nb] the current policy's log-probabilities (forward output)
+  const float* lp_camera;  // [M][nc]
+  const float* prior_buttons;   // optional [M][nb] / [M][nc] log-probabilities of the frozen prior (both or neither; null: no KL term, K = 0)
+  const float* prior_camera;
+  const long* act_buttons; // [M]; only compared with column indices (an out-of-range label matches nothing)
+  const long* act_camera;  // [M]
+  const float* old_log_prob;    // [M] the behaviour policy's lp_b[a_b] + lp_c[a_c]
+  const float* advantage;  // [M]
+  const float* value;      // optional: the raw value output (normalised space) of frame r at value[r * value_stride]; null: no value term
+  const float* value_target;    // [M] denormalised returns (read only with `value`)
+  const float* vnorm;      // device [2]: the value normaliser's (mean, std) (read only with `value`)
+  const float* weight;     // optional [M] per-frame weights (null: all ones); a row with weight 0 writes exact zeros to dz and to its slab record
+  vpt_op16* dz;            // optional [M][ldz], ldz >= nb + nc + 1: policy columns, the value column, further columns zero
+  float* frame_out;        // optional [M][16]: surrogate, K_b, K_c, H_b, H_c, (v - t^)^2, rho, clipped, lp, old_lp - lp, w, w > 0, 0 x 4 (unweighted)
+  float* slab;             // set by the launcher: [M][16] weighted records, summed by vpt_slab_sum into the totals
+  long value_stride;
+  int M, nb, nc, ldz;
+  float clip, kl_coef, entropy_coef, value_coef, inv_temp, scale;
+};
+
+struct VptGaeArgs {         // generalised advantage estimation, one lane per sequence (vpt_gae_kernel)
+  const float* reward;     // [B][T]
+  const float* value;      // [B][T] denormalised value predictions
+  const uint8_t* first;    // [B][T] frame t starts an episode
+  const float* last_value; // [B] V of the frame after the rollout
+  const uint8_t* next_first;    // [B] that frame starts an episode
+  float* adv;              // [B][T]
+  float* ret;              // [B][T] adv + value
+  int B, T;
+  float gamma, lam;
+};
+
 struct VptFullAttnBwdArgs { // backward of vpt_attn_kernel with causal = 0 (mask "none", no memory, no bias): vpt_full_attn_bwd_kernel
   const float* qkv;        // forward projections [B*t][ld]: Q | K | V
   const float* dout;       // [B*t][hid]
@@ -463,6 +496,9 @@ int vpt_nll_bwd_launch(const VptNllBwdArgs* a, hipStream_t s);
 long vpt_bc_loss_workspace_floats(int M);
 int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* workspace, hipStream_t s);
 int vpt_idm_loss_launch(const VptIdmLossArgs* a, float* totals, float* workspace, hipStream_t s);
+long vpt_rl_loss_workspace_floats(int M);
+int vpt_rl_loss_launch(const VptRlLossArgs* a, float* totals, float* workspace, hipStream_t s);
+int vpt_gae_launch(const VptGaeArgs* a, hipStream_t s);
 int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t s);
 long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid);
 int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);

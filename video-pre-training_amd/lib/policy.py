@@ -118,11 +118,12 @@ class MinecraftPolicy(nn.Module):
 
 
 class NormalizeEwma(nn.Module):
-    """Buffers and denormalisation of lib/normalize_ewma.py:8-31,57-60 (parameters with requires_grad=False)."""
+    """Buffers, update and (de)normalisation of lib/normalize_ewma.py:8-60 (parameters with requires_grad=False)."""
 
-    def __init__(self, input_shape, epsilon=1e-5):
+    def __init__(self, input_shape, epsilon=1e-5, beta=0.99999):
         super().__init__()
         self.epsilon = epsilon
+        self.beta = beta
         self.running_mean = nn.Parameter(torch.zeros(input_shape, dtype=torch.float), requires_grad=False)
         self.running_mean_sq = nn.Parameter(torch.zeros(input_shape, dtype=torch.float), requires_grad=False)
         self.debiasing_term = nn.Parameter(torch.tensor(0.0, dtype=torch.float), requires_grad=False)
@@ -136,6 +137,35 @@ class NormalizeEwma(nn.Module):
     def denormalize(self, x):
         mean, var = self.running_mean_var()
         return x * torch.sqrt(var)[(None,) * 2] + mean[(None,) * 2]
+
+    @torch.no_grad()
+    def update(self, x, weight=None):
+        """The statistics update of the reference's training-mode forward (lib/normalize_ewma.py:37-52 with per_element_update=False), in place on
+        the three buffers: x [..., *input_shape], batch moments over the leading axes.  weight (one per leading position, finite, non-negative):
+        the batch moments are sum w x / sum w, and a zero-weight position counts nothing whatever it holds.  In-place ops: the buffers' versions
+        move, so affine() -- and with it the captured acting graph -- is refreshed."""
+        x = x.detach().to(torch.float)
+        axes = tuple(range(x.dim() - self.running_mean.dim()))
+        if weight is None:
+            batch_mean = x.mean(dim=axes)
+            batch_sq_mean = (x ** 2).mean(dim=axes)
+        else:
+            w = weight.detach().to(device=x.device, dtype=torch.float).reshape(x.shape[:len(axes)] + (1,) * self.running_mean.dim())
+            live = w != 0
+            wsum = w.sum()
+            batch_mean = torch.where(live, w * x, torch.zeros_like(x)).sum(dim=axes) / wsum
+            batch_sq_mean = torch.where(live, w * x ** 2, torch.zeros_like(x)).sum(dim=axes) / wsum
+        weight_ = self.beta
+        self.running_mean.mul_(weight_).add_(batch_mean * (1.0 - weight_))
+        self.running_mean_sq.mul_(weight_).add_(batch_sq_mean * (1.0 - weight_))
+        self.debiasing_term.mul_(weight_).add_(1.0 * (1.0 - weight_))
+
+    def normalize(self, x):
+        """lib/normalize_ewma.py:54-55 (the forward without the update)."""
+        x = x.to(torch.float)
+        mean, var = self.running_mean_var()
+        lead = (None,) * (x.dim() - mean.dim())
+        return (x - mean[lead]) / torch.sqrt(var)[lead]
 
     def affine(self):
         """denormalize(x) = x * scale + shift with (scale, shift) as host floats, recomputed only when the statistics change
@@ -161,6 +191,9 @@ class ScaledMSEHead(nn.Module):
 
     def denormalize(self, x):
         return self.normalizer.denormalize(x)
+
+    def normalize(self, x):
+        return self.normalizer.normalize(x)
 
 
 class _PolicyForwardFn(torch.autograd.Function):

@@ -71,7 +71,7 @@ def _call(name, meta, *args, fmt="bf16", label=None):
 
 WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
 WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
-WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD = 11, 12
+WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD, WS_RL_LOSS = 11, 12, 13
 FULL_ATTENTION_MAX_T = 160      # the mask="none" attention kernels' longest window (forward and backward)
 
 
@@ -962,6 +962,75 @@ def idm_loss(lp_buttons, lp_camera, act_buttons, act_camera, scale, weight=None,
     _call("vpt_idm_loss", dict(bytes=(8.0 * (gb * nb + gc * nc) + (2.0 * ldz if want_dz else 0.0)) * m), ptr(lp_buttons), ptr(lp_camera), ptr(act_buttons),
           ptr(act_camera), ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws), m, gb, nb, gc, nc, ldz, ctypes.c_float(scale), _stream(), fmt=fmt)
     return dz, frame_out, totals
+
+
+def rl_loss(lp_buttons, lp_camera, act_buttons, act_camera, old_log_prob, advantage, ldz, scale, *, prior_buttons=None, prior_camera=None,
+            value=None, value_target=None, vnorm=None, weight=None, clip=0.2, kl_coef=0.0, entropy_coef=0.0, value_coef=0.5, temperature=1.0,
+            dtype=torch.bfloat16, want_dz=True, want_frames=True, want_totals=True):
+    """The fine-tuning loss in one launch (vpt_rl_loss) -> (dz | None, frame_out | None, totals | None): clipped policy gradient + kl_coef x
+    KL(pi || prior) - entropy_coef x entropy + value_coef x (v - normalised target)^2, per frame, weighted mean over the frames.
+    lp_* / prior_* fp32 [M, n] log-probs (the priors both or neither); act_* int64 [M]; old_log_prob, advantage fp32 [M]; value: fp32 [M] VIEW of the raw
+    value output (any positive stride -- S["logits"][:, nb + nc]) with value_target fp32 [M] (denormalised) and vnorm fp32 [2] = (mean, std) on the
+    device, or None (no value term); weight fp32 [M] or None (all ones).
+    dz: 16-bit [M, ldz], ldz >= nb + nc + 1 (a zero-weight row: exact zeros); frame_out fp32 [M, 16] = surrogate, K_b, K_c, H_b, H_c, (v - t^)^2, rho,
+    clipped, lp, old_lp - lp, w, w > 0, 0 x 4 (unweighted); totals fp32 [16] = sum_r w frame_out[r, :10], sum w, rows with w > 0, 0 x 4.  `scale`
+    carries 1 / sum w (and the fp16 loss scale); the temperature is applied by the kernel.  tests/rl_loss_ref.py is the fp64 host reference."""
+    for t, nme in ((lp_buttons, "lp_buttons"), (lp_camera, "lp_camera"), (prior_buttons, "prior_buttons"), (prior_camera, "prior_camera"),
+                   (old_log_prob, "old_log_prob"), (advantage, "advantage"), (value_target, "value_target"), (vnorm, "vnorm"), (weight, "weight")):
+        _chk(t, torch.float32, nme)
+    _chk(act_buttons, torch.int64, "act_buttons"); _chk(act_camera, torch.int64, "act_camera")
+    if lp_buttons.dim() != 2 or lp_camera.dim() != 2:
+        raise ValueError("rl_loss: log-probs must be [M, classes]")
+    m, nb = lp_buttons.shape
+    nc = lp_camera.shape[1]
+    per_frame = [act_buttons, act_camera, old_log_prob, advantage] + [t for t in (weight, value, value_target) if t is not None]
+    if lp_camera.shape[0] != m or any(t.numel() != m for t in per_frame):
+        raise ValueError(f"rl_loss: every per-frame tensor must have {m} rows")
+    if (prior_buttons is None) != (prior_camera is None):
+        raise ValueError("rl_loss: give both prior_buttons and prior_camera or neither")
+    if prior_buttons is not None and (prior_buttons.shape != lp_buttons.shape or prior_camera.shape != lp_camera.shape):
+        raise ValueError("rl_loss: the prior's log-probs must have the policy's shapes")
+    stride = 0
+    if value is not None:
+        if not value.is_cuda or value.dtype != torch.float32 or value.dim() != 1 or (m > 1 and value.stride(0) < 1):
+            raise ValueError("rl_loss: value must be a 1-D fp32 GPU tensor (or view) with a positive stride")
+        if value_target is None or vnorm is None or vnorm.numel() != 2:
+            raise ValueError("rl_loss: the value term needs value_target [M] and vnorm [2] = (mean, std) on the device")
+        stride = value.stride(0) if m > 1 else 1
+    if not temperature > 0:
+        raise ValueError("rl_loss: temperature must be positive")
+    dt, fmt = _fmt(dtype=dtype)
+    dev = lp_buttons.device
+    dz = torch.empty(m, ldz, dtype=dt, device=dev) if want_dz else None
+    frame_out = torch.empty(m, 16, dtype=torch.float32, device=dev) if want_frames else None
+    totals = torch.empty(16, dtype=torch.float32, device=dev) if want_totals else None
+    ws = _workspace(WS_RL_LOSS, m, device=dev, fmt=fmt) if want_totals else None
+    reads = (2 if want_dz else 1) * 4.0 * (nb + nc) * (2 if prior_buttons is not None else 1)
+    f = ctypes.c_float
+    _call("vpt_rl_loss", dict(bytes=(reads + (2.0 * ldz if want_dz else 0.0)) * m), ptr(lp_buttons), ptr(lp_camera), ptr(prior_buttons), ptr(prior_camera),
+          ptr(act_buttons), ptr(act_camera), ptr(old_log_prob), ptr(advantage), ptr(value), ctypes.c_int64(stride), ptr(value_target), ptr(vnorm),
+          ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws), m, nb, nc, ldz, f(clip), f(kl_coef), f(entropy_coef), f(value_coef),
+          f(temperature), f(scale), _stream(), fmt=fmt)
+    return dz, frame_out, totals
+
+
+def gae(reward, value, first, last_value, next_first, gamma=0.999, lam=0.95):
+    """Generalised advantage estimation (vpt_gae) -> (adv, ret) fp32 [B, T].  reward, value fp32 [B, T] (value denormalised); first bool / uint8 [B, T]
+    (frame t starts an episode); last_value fp32 [B], next_first bool / uint8 [B]: the frame after the rollout.  tests/gae_ref.py is the float32 host
+    twin (bit for bit)."""
+    _chk(reward, torch.float32, "reward"); _chk(value, torch.float32, "value"); _chk(last_value, torch.float32, "last_value")
+    if reward.dim() != 2 or value.shape != reward.shape or first.shape != reward.shape:
+        raise ValueError(f"gae: reward, value and first must share one [B, T] shape, got {tuple(reward.shape)}, {tuple(value.shape)}, {tuple(first.shape)}")
+    b, t = reward.shape
+    if last_value.numel() != b or next_first.numel() != b:
+        raise ValueError(f"gae: last_value and next_first must hold {b} elements")
+    first8 = (first.view(torch.uint8) if first.dtype == torch.bool else first).contiguous()
+    next8 = (next_first.view(torch.uint8) if next_first.dtype == torch.bool else next_first).contiguous()
+    _chk(first8, torch.uint8, "first"); _chk(next8, torch.uint8, "next_first")
+    adv, ret = torch.empty_like(reward), torch.empty_like(reward)
+    _call("vpt_gae", dict(bytes=17.0 * b * t), ptr(reward), ptr(value), ptr(first8), ptr(last_value), ptr(next8), ptr(adv), ptr(ret), b, t,
+          ctypes.c_float(gamma), ctypes.c_float(lam), _stream())
+    return adv, ret
 
 
 def conv_backward_prepare(dy, y, res, stats_in, edge_sa, edge_sg, cin, dpooled=None, argmax=None, d_sa=None, d_sg=None, want_t12=False):
