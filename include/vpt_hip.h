@@ -357,6 +357,29 @@ int vpt_adam_step_multi(const void* table, int ntensors, int64_t total_blocks, i
  * torch.cuda.amp.GradScaler.unscale_ computes for an fp16 run of behavioural_cloning.py:117-122. */
 int vpt_grads_nonfinite_multi(const void* table, int ntensors, int64_t total_blocks, int32_t* flag, void* stream);
 
+/* Global-norm gradient clipping: th.nn.utils.clip_grad_norm_(params, MAX_GRAD_NORM) as behavioural_cloning.py:121 meant it (upstream
+ * passes an exhausted generator, so the call does nothing there).  One read of the gradients over the SAME table as vpt_adam_step_multi
+ * (only `grad`, `n`, `first_block` are read), fixed summation order, fp64 finish, no host round trip:
+ *   norm_out[0] = || grad * grad_scale ||_2 over all tensors (fp32 squares, fp32 sum per 1024-element block, fp64 above that);
+ *   norm_out[1] = min((1 / (norm + 1e-6)) * max_norm, 1) in fp32, torch's clip_coef_clamped; 1 when max_norm <= 0 (norm only);
+ *                 0 when the squared sum is not finite;
+ *   norm_out[2] = 1 if the squared sum is not finite, else 0;   norm_out[3] = 0.
+ * per_tensor (optional, fp32 [ntensors]): each tensor's own norm.  flag (optional device int32, zeroed by the caller): set, never
+ * cleared, when the sum is not finite or any raw gradient is inf / nan -- with it this call replaces vpt_grads_nonfinite_multi.
+ * workspace: vpt_grad_norm_workspace_bytes(ntensors, total_blocks) bytes, 8-byte aligned, caller-owned.  (Today it is left holding
+ * the intermediate sums -- [ntensors] fp64 per-tensor squared sums, then [total_blocks] fp32 block partials -- which the tests read;
+ * that layout is NOT part of this interface and may change.) */
+long vpt_grad_norm_workspace_bytes(int ntensors, int64_t total_blocks);
+int vpt_grad_norm_multi(const void* table, int ntensors, int64_t total_blocks, float grad_scale, float max_norm, void* workspace,
+                        float* norm_out, float* per_tensor, int32_t* flag, void* stream);
+
+/* vpt_adam_step_multi with the gradient also multiplied by the DEVICE scalar *clip_coef (norm_out + 1 of vpt_grad_norm_multi):
+ * g' = (g * grad_scale) * coef + wd * p.  clip_grad_norm_ + Adam.step() of behavioural_cloning.py:121-122 without the in-place
+ * scaling pass.  A coefficient of exactly 1 gives vpt_adam_step_multi's result bit for bit. */
+int vpt_adam_step_multi_clip(const void* table, int ntensors, int64_t total_blocks, int step, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, const float* clip_coef,
+                             void* stream);
+
 /* ---- behavioural-cloning step: backward of the heads / trunk / transformer (the reference uses torch autograd,
  * behavioural_cloning.py:117-119).  Linear layers reuse vpt_linear_forward (dgrad: W^T packed; wgrad: A = dY^T). */
 

@@ -81,6 +81,9 @@ SIGNATURES = {
     "vpt_adam_step": [_P, _P, _P, _P, ctypes.c_uint64, _I, _F, _F, _F, _F, _F, _F, _P],
     "vpt_adam_step_multi": [_P, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P],
     "vpt_grads_nonfinite_multi": [_P, _I, _L, _P, _P],
+    "vpt_grad_norm_workspace_bytes": [_I, ctypes.c_int64],
+    "vpt_grad_norm_multi": [_P, _I, _L, _F, _F, _P, _P, _P, _P, _P],
+    "vpt_adam_step_multi_clip": [_P, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P],
     "vpt_layernorm_linear_forward": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vpt_masked_attention_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_masked_attention_step_inplace": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -135,6 +138,8 @@ def load(fmt: str = "bf16"):
     lib.vpt_version.restype = ctypes.c_char_p
     lib.vpt_operand_format.restype = ctypes.c_char_p
     lib.vpt_conv3x3_wgrad_scratch_floats.restype = ctypes.c_long
+    if hasattr(lib, "vpt_grad_norm_workspace_bytes"):
+        lib.vpt_grad_norm_workspace_bytes.restype = ctypes.c_long
     lib.vpt_workspace_bytes.argtypes, lib.vpt_workspace_bytes.restype = [_I] * 6, ctypes.c_int64
     lib.vpt_conv3x3_pool_seam_elems.argtypes, lib.vpt_conv3x3_pool_seam_elems.restype = [_I] * 4, ctypes.c_int64
     for q, at in (("vpt_conv3x3_packed_elems", [_I, _I]), ("vpt_conv3x3_table_floats", [_I]), ("vpt_linear_packed_elems", [_I, _I]),

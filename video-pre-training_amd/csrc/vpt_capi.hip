@@ -527,16 +527,41 @@ int vpt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
   CHECK_LAUNCH(vpt_adam_launch(&a, (hipStream_t)stream), "vpt_adam_step");
 }
 
-int vpt_adam_step_multi(const void* table, int ntensors, int64_t total_blocks, int step, float lr, float beta1, float beta2,
-                        float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, void* stream) {
+static int adam_step_multi_impl(const char* who, const void* table, int ntensors, int64_t total_blocks, int step, float lr, float beta1, float beta2,
+                                float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, const float* clip_coef, void* stream) {
   if (step < 1) return fail(-1, "vpt_adam_step_multi: step counts from 1");
   if (!table && ntensors > 0) return fail(-1, "vpt_adam_step_multi: null table");
   VptAdamArgs a = {};
-  a.p = nullptr; a.g = nullptr; a.m = nullptr; a.v = nullptr; a.n = 0; a.skip_flag = (const int*)skip_flag;
+  a.p = nullptr; a.g = nullptr; a.m = nullptr; a.v = nullptr; a.n = 0; a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
   a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
   a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
-  CHECK_LAUNCH(vpt_adam_multi_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, &a, (hipStream_t)stream), "vpt_adam_step_multi");
+  CHECK_LAUNCH(vpt_adam_multi_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, &a, (hipStream_t)stream), who);
+}
+
+int vpt_adam_step_multi(const void* table, int ntensors, int64_t total_blocks, int step, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, void* stream) {
+  return adam_step_multi_impl("vpt_adam_step_multi", table, ntensors, total_blocks, step, lr, beta1, beta2, eps, weight_decay, grad_scale, skip_flag, nullptr, stream);
+}
+
+int vpt_adam_step_multi_clip(const void* table, int ntensors, int64_t total_blocks, int step, float lr, float beta1, float beta2,
+                             float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, const float* clip_coef, void* stream) {
+  if (!clip_coef) return fail(-1, "vpt_adam_step_multi_clip: null clip_coef (vpt_adam_step_multi is the unclipped entry)");
+  return adam_step_multi_impl("vpt_adam_step_multi_clip", table, ntensors, total_blocks, step, lr, beta1, beta2, eps, weight_decay, grad_scale, skip_flag, clip_coef, stream);
+}
+
+long vpt_grad_norm_workspace_bytes(int ntensors, int64_t total_blocks) {
+  const long f = vpt_grad_norm_workspace_floats(ntensors, (long)total_blocks);
+  return f < 0 ? -1 : 4 * f;
+}
+
+int vpt_grad_norm_multi(const void* table, int ntensors, int64_t total_blocks, float grad_scale, float max_norm, void* workspace, float* norm_out,
+                        float* per_tensor, int32_t* flag, void* stream) {
+  if (!table || ntensors <= 0 || total_blocks < 0) return fail(-1, "vpt_grad_norm_multi: null table / no tensors");
+  if (!workspace || !norm_out) return fail(-1, "vpt_grad_norm_multi: null workspace / norm_out");
+  if (((uintptr_t)workspace & 7) != 0) return fail(-1, "vpt_grad_norm_multi: workspace must be 8-byte aligned");
+  CHECK_LAUNCH(vpt_grad_norm_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, grad_scale, max_norm, (float*)workspace, norm_out, per_tensor,
+                                    (int*)flag, (hipStream_t)stream), "vpt_grad_norm_multi");
 }
 
 int vpt_grads_nonfinite_multi(const void* table, int ntensors, int64_t total_blocks, int32_t* flag, void* stream) {

@@ -467,6 +467,8 @@ struct VptAdamArgs {
   float inv_sqrt_bc2;      // 1 / sqrt(1 - beta2^t)
   const int* skip_flag;    // optional device flag (multi-tensor form): non-zero = leave every tensor untouched (a loss-scaled step
                            // whose gradients overflowed, vpt_grads_nonfinite_multi)
+  const float* clip_coef;  // optional device scalar (multi-tensor form): the gradient-norm clip coefficient, norm_out + 1 of vpt_grad_norm_launch;
+                           // gk = fmaf(wd, p, (g * grad_scale) * coef).  Null: the unclipped expression, bit for bit
 };
 
 extern "C" {
@@ -476,6 +478,9 @@ int vpt_chw_to_blocked_launch(const float* src, float* dst, long rows, int C, in
 int vpt_adam_launch(const VptAdamArgs* a, hipStream_t s);
 int vpt_adam_multi_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, const VptAdamArgs* h, hipStream_t s);
 int vpt_grads_nonfinite_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, int* flag, hipStream_t s);
+long vpt_grad_norm_workspace_floats(int ntensors, long total_blocks);
+int vpt_grad_norm_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, float grad_scale, float max_norm, float* workspace,
+                         float* norm_out, float* per_tensor, int* flag, hipStream_t s);
 int vpt_affine_bwd_launch(const VptAffineBwdArgs* a, int pass, hipStream_t s);
 long vpt_affine_bwd_partial_floats(int frames, int CB, int HW, int per_element, int pass);
 int vpt_pool_bwd_launch(const VptPoolBwdArgs* a, hipStream_t s);

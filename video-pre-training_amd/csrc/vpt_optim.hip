@@ -51,6 +51,9 @@ extern "C" int vpt_adam_launch(const VptAdamArgs* a, hipStream_t stream) {
 // ---- multi-tensor form: ONE launch updates every parameter tensor of the model (129 on the 2x policy; the per-tensor form cost
 // 129 launches of ~15 us for 2 ms of HBM traffic).  `table` is a device array of descriptors sorted by first_block; block b
 // finds its tensor by binary search and handles 1024 elements of it (256 threads x float4).
+// CLIP: the gradient is also multiplied by the device scalar *h.clip_coef (global-norm clipping, vpt_grad_norm.hip), (g * grad_scale) * coef in that
+// association; without it the instantiation is the unclipped kernel, expression for expression.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void vpt_adam_multi_kernel(const VptAdamTensor* __restrict__ table, int ntensors, VptAdamArgs h) {
   int lo = 0, hi = ntensors - 1;
   const long b = blockIdx.x;
@@ -62,12 +65,13 @@ __global__ __launch_bounds__(256) void vpt_adam_multi_kernel(const VptAdamTensor
   const VptAdamTensor t = table[lo];
   const size_t i0 = ((size_t)(b - t.first_block) * 256 + threadIdx.x) * 4;
   const float c1 = 1.0f - h.beta1, c2 = 1.0f - h.beta2;
+  const float coef = CLIP ? *h.clip_coef : 1.0f;
   if (i0 + 4 <= t.n) {   // 16-byte accesses like vpt_adam_kernel (views may start at any element: unaligned dwordx4 is legal on gfx950)
     f32x4 p = *(const f32x4*)(t.p + i0), g = *(const f32x4*)(t.g + i0);
     f32x4 m = *(const f32x4*)(t.m + i0), v = *(const f32x4*)(t.v + i0);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float gk = fmaf(h.weight_decay, p[k], g[k] * h.grad_scale);
+      const float gk = fmaf(h.weight_decay, p[k], CLIP ? (g[k] * h.grad_scale) * coef : g[k] * h.grad_scale);
       m[k] = fmaf(h.beta1, m[k], c1 * gk);
       v[k] = fmaf(h.beta2, v[k], c2 * gk * gk);
       const float denom = sqrtf(v[k]) * h.inv_sqrt_bc2 + h.eps;
@@ -80,7 +84,7 @@ __global__ __launch_bounds__(256) void vpt_adam_multi_kernel(const VptAdamTensor
   }
   for (size_t i = i0; i < t.n; ++i) {   // the tensor's last (partial) group of four
     const float pk = t.p[i];
-    const float gk = fmaf(h.weight_decay, pk, t.g[i] * h.grad_scale);
+    const float gk = fmaf(h.weight_decay, pk, CLIP ? (t.g[i] * h.grad_scale) * coef : t.g[i] * h.grad_scale);
     const float m = fmaf(h.beta1, t.m[i], c1 * gk), v = fmaf(h.beta2, t.v[i], c2 * gk * gk);
     t.m[i] = m; t.v[i] = v;
     t.p[i] = pk - h.step_size * (m / (sqrtf(v) * h.inv_sqrt_bc2 + h.eps));
@@ -90,7 +94,8 @@ __global__ __launch_bounds__(256) void vpt_adam_multi_kernel(const VptAdamTensor
 extern "C" int vpt_adam_multi_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, const VptAdamArgs* h, hipStream_t stream) {
   if (ntensors <= 0 || total_blocks <= 0) return 0;
   if (total_blocks > 0x7fffffffL) return -2;
-  hipLaunchKernelGGL(vpt_adam_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, stream, table_dev, ntensors, *h);
+  if (h->clip_coef) hipLaunchKernelGGL(vpt_adam_multi_kernel<true>, dim3((unsigned)total_blocks), dim3(256), 0, stream, table_dev, ntensors, *h);
+  else hipLaunchKernelGGL(vpt_adam_multi_kernel<false>, dim3((unsigned)total_blocks), dim3(256), 0, stream, table_dev, ntensors, *h);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

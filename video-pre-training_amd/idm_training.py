@@ -36,8 +36,11 @@ class IDMTrainer(CnnTrainingMixin):
     dense_tiling = "throughput"  # as IDMEngine: the MFMA GEMM whatever the row count (a one-window chunk of <= 8 frames would take the GEMV kernel)
 
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
-                 optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200, train_cnn: bool = False):
-        """policy: lib.policy.InverseActionPolicy on the GPU.  Trainable: `net.img_process.linear.*`, `net.pre_lstm_ln.*` (when configured), every
+                 optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200, train_cnn: bool = False,
+                 max_grad_norm: Optional[float] = None):
+        """max_grad_norm: global-norm gradient clipping as BCTrainer's (None = off, the default; float("inf") = measure only; a non-finite norm skips
+        the step on the device in both formats).
+        policy: lib.policy.InverseActionPolicy on the GPU.  Trainable: `net.img_process.linear.*`, `net.pre_lstm_ln.*` (when configured), every
         `net.recurrent_layer.blocks.*` tensor, `net.final_ln.*`, `pi_head.buttons.*`, `pi_head.camera.*`.  train_cnn=False (default) freezes
         `net.conv3d_layer.*` and every `net.img_process.cnn.*` tensor (the dense layer included) and launches what it always launched.
         train_cnn=True trains those 49 tensors as well: per chunk of whole windows (the engine's cnn_chunk granularity) ops.conv3d_t5 with x0 kept, the
@@ -51,6 +54,7 @@ class IDMTrainer(CnnTrainingMixin):
         defaults to 256 (1 = off in bf16), the loss gradient is written as loss_scale / temperature x (softmax - one-hot) per frame, the optimiser
         launch un-scales, an overflowed step is skipped on the device, the scale halves then and doubles after `scale_growth_interval` clean steps."""
         self.train_cnn = bool(train_cnn)
+        self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
         self.policy = policy
         self.engine = policy._engine
         self.dtype = self.engine.dtype
@@ -77,7 +81,8 @@ class IDMTrainer(CnnTrainingMixin):
     def state_dict(self) -> dict:
         self._need_optimizer_state()
         return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
-                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, exp_avg={n: t.detach().clone() for n, t in self.m.items()},
+                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
+                    exp_avg={n: t.detach().clone() for n, t in self.m.items()},
                     exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
 
     def _need_optimizer_state(self):
@@ -88,6 +93,8 @@ class IDMTrainer(CnnTrainingMixin):
         self._need_optimizer_state()
         if self.scaled and "loss_scale" in sd:
             self.loss_scale = float(sd["loss_scale"])
+        if "max_grad_norm" in sd:
+            self.max_grad_norm = self._checked_max_grad_norm(sd["max_grad_norm"])
         if set(sd["exp_avg"]) != set(self.m):
             raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
         self.step_count = int(sd["step"])
@@ -336,25 +343,9 @@ class IDMTrainer(CnnTrainingMixin):
     @torch.no_grad()
     def step(self, img_u8, buttons, camera, *, frame_weight=None, metrics: Optional[dict] = None) -> float:
         """One Adam step (ops.adam_step_multi_: one launch for all tensors; in the fp16 mode it un-scales the gradients and leaves every tensor
-        untouched when the overflow check fired).  Returns the loss.  The policy's next predict / label_video sees the new weights."""
+        untouched when the overflow check fired; with max_grad_norm set the gradients are clipped by their global norm inside that launch and metrics gains
+        grad_norm / clip_coef / grad_norm_per_tensor -- CnnTrainingMixin._optimizer_tail).  Returns the loss.  The policy's next predict / label_video sees the new weights."""
         self._need_optimizer_state()
         loss, grads = self.loss_and_grads(img_u8, buttons, camera, frame_weight=frame_weight, metrics=metrics, unscaled=False)
-        names = [n for n in self.trainable if n in grads]
-        found_inf = torch.zeros(1, dtype=torch.int32, device=img_u8.device) if self.scaled else None
-        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
-                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
-                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                             grad_scale=self.grad_unscale(self._weight_sum), found_inf=found_inf)
-        loss = float(loss)                     # (synchronises: the flag below is ready)
-        if self.scaled and int(found_inf.item()):
-            self.skipped_steps += 1
-            self._clean_steps = 0
-            self.loss_scale = max(self.loss_scale * 0.5, 1.0)
-            return loss
-        self.step_count += 1
-        if self.scaled:
-            self._clean_steps += 1
-            if self._clean_steps >= self.scale_growth_interval:
-                self._clean_steps, self.loss_scale = 0, min(self.loss_scale * 2.0, 65536.0)
-        self.policy._packed_key = None  # weights changed (in place, behind autograd's version counters): re-pack before the next forward
+        loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._weight_sum), img_u8.device, metrics)
         return loss

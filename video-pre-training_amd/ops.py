@@ -774,52 +774,109 @@ def adam_step_(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.99
           ctypes.c_float(grad_scale), _stream())
 
 
+def _adam_table(grads, params=None, exp_avgs=None, exp_avg_sqs=None):
+    """The device table of VptAdamTensor descriptors (include/vpt_hip.h: vpt_adam_step_multi) the multi-tensor launches share -> (table uint8
+    tensor, total 1024-element blocks, total elements).  With `grads` alone the other three pointers are null (the launches that only read gradients)."""
+    import numpy as np
+    rec = np.zeros(len(grads), dtype=[("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<u8"), ("fb", "<i8")])
+    blk = numel = 0
+    for i, g in enumerate(grads):
+        _chk(g, torch.float32, "grad")
+        n = g.numel()
+        if params is None:
+            assert g.is_contiguous()
+            rec[i] = (0, g.data_ptr(), 0, 0, n, blk)
+        else:
+            p, m, v = params[i], exp_avgs[i], exp_avg_sqs[i]
+            for t, nme in ((p, "param"), (g, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
+                _chk(t, torch.float32, nme)
+                assert t.is_contiguous()
+            assert p.numel() == n and m.numel() == n and v.numel() == n
+            rec[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, blk)
+        blk += (n + 1023) // 1024
+        numel += n
+    table = torch.from_numpy(rec.view(np.uint8)).to(grads[0].device, non_blocking=False)
+    return table, blk, numel
+
+
+def _grad_norm_workspace(n_t, blk, device):
+    """vpt_grad_norm_multi's scratch: vpt_grad_norm_workspace_bytes(n_t, blk) bytes, 8-byte aligned (fp64 sums in front of an fp32 array whose length may
+    be odd: the byte count is rounded UP to whole doubles)."""
+    nbytes = int(_native.load("bf16").vpt_grad_norm_workspace_bytes(n_t, blk))
+    if nbytes < 0:
+        raise RuntimeError(f"vpt_grad_norm_workspace_bytes({n_t}, {blk}) failed")
+    return torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=device)
+
+
+def _grad_norm_launch(table, n_t, blk, numel, scale, max_norm, norm_out, per_tensor, flag):
+    """vpt_grad_norm_multi over a table already on the device (norm kernel + the two fp64 finish launches); max_norm None: the norm only."""
+    ws = _grad_norm_workspace(n_t, blk, table.device)
+    _call("vpt_grad_norm_multi", dict(bytes=4.0 * numel + 8.0 * blk), ptr(table), n_t, blk, ctypes.c_float(scale),
+          ctypes.c_float(0.0 if max_norm is None else max_norm), ptr(ws), ptr(norm_out), ptr(per_tensor), ptr(flag), _stream())
+    return ws
+
+
+def grad_norm(grads, scale=1.0, max_norm=None, per_tensor=False, flag=None):
+    """fp32 [4] device tensor (norm, clip coefficient, non-finite, 0) of the fp32 tensors in `grads` -- the global l2 norm of grads * scale and
+    torch.nn.utils.clip_grad_norm_'s clip_coef_clamped for `max_norm` (None: 1.0, the norm only; behavioural_cloning.py:121) -- and, with
+    per_tensor=True, a second fp32 [len(grads)] tensor of each tensor's own norm.  Three dependent launches (vpt_grad_norm_multi), fixed summation
+    order, no host synchronisation: for callers of loss_and_grads who bring their own optimiser.  flag: optional int32 [1] device tensor, SET (never
+    cleared: the caller zeroes it) when the squared sum is not finite or any gradient is inf / nan; the coefficient is then 0."""
+    grads = [g if g.is_contiguous() else g.contiguous() for g in grads if g is not None]
+    if not grads:
+        raise ValueError("grad_norm: no gradient tensors")
+    _chk(flag, torch.int32, "flag")
+    table, blk, numel = _adam_table(grads)
+    norm_out = torch.empty(4, dtype=torch.float32, device=grads[0].device)
+    per = torch.empty(len(grads), dtype=torch.float32, device=grads[0].device) if per_tensor else None
+    _grad_norm_launch(table, len(grads), blk, numel, scale, max_norm, norm_out, per, flag)
+    return (norm_out, per) if per_tensor else norm_out
+
+
 def adam_step_multi_(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0,
-                     found_inf=None):
+                     found_inf=None, max_grad_norm=None, norm_out=None, per_tensor_norms=None):
     """The Adam update of adam_step_ for a list of tensors in ONE launch (flat fp32 views; same arithmetic per element).
     found_inf: optional int32 [1] device tensor (loss-scaled fp16 step).  It is zeroed, set by vpt_grads_nonfinite_multi when any
-    gradient is inf / nan, and read by the Adam launch, which then leaves every tensor untouched -- no host round trip."""
-    import numpy as np
+    gradient is inf / nan, and read by the Adam launch, which then leaves every tensor untouched -- no host round trip.
+    max_grad_norm (None: off, exactly the launches above): global-norm clipping of grads * grad_scale (clip_grad_norm_ + Adam.step(),
+    behavioural_cloning.py:121-122).  vpt_grad_norm_multi runs over the same table -- with found_inf as its flag it REPLACES the non-finite launch --
+    and the Adam launch multiplies by the coefficient it left on the device (vpt_adam_step_multi_clip); float("inf") measures and never clips.
+    A non-finite norm sets found_inf (pass one: without it the update would carry the non-finite gradients on).  norm_out (fp32 [4]) and
+    per_tensor_norms (fp32 [len(params)]) receive ops.grad_norm's results; pass norm_out to read them (a scratch one is used otherwise).
+    Returns the table (keep it alive until the launch has been enqueued; the caller may drop it afterwards: stream-ordered free)."""
     n_t = len(params)
     if n_t == 0:
         return
     _chk(found_inf, torch.int32, "found_inf")
-    rec = np.zeros(n_t, dtype=[("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<u8"), ("fb", "<i8")])
-    blk = 0
-    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
-        for t, nme in ((p, "param"), (g, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
-            _chk(t, torch.float32, nme)
-            assert t.is_contiguous()
-        n = p.numel()
-        assert g.numel() == n and m.numel() == n and v.numel() == n
-        rec[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, blk)
-        blk += (n + 1023) // 1024
-    table = torch.from_numpy(rec.view(np.uint8)).to(params[0].device, non_blocking=False)
+    table, blk, numel = _adam_table(grads, params, exp_avgs, exp_avg_sqs)
+    hyper = (int(step), ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(weight_decay),
+             ctypes.c_float(grad_scale), ptr(found_inf))
     if found_inf is not None:
         found_inf.zero_()
-        _call("vpt_grads_nonfinite_multi", dict(bytes=4.0 * sum(p.numel() for p in params)), ptr(table), n_t, blk, ptr(found_inf), _stream())
-    _call("vpt_adam_step_multi", dict(bytes=28.0 * sum(p.numel() for p in params)), ptr(table), n_t, blk, int(step),
-          ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(weight_decay),
-          ctypes.c_float(grad_scale), ptr(found_inf), _stream())
-    return table   # keep alive until the launch has been enqueued (the caller may drop it afterwards: stream-ordered free)
+    if max_grad_norm is None:
+        if found_inf is not None:
+            _call("vpt_grads_nonfinite_multi", dict(bytes=4.0 * numel), ptr(table), n_t, blk, ptr(found_inf), _stream())
+        _call("vpt_adam_step_multi", dict(bytes=28.0 * numel), ptr(table), n_t, blk, *hyper, _stream())
+        return table   # keep alive until the launch has been enqueued (the caller may drop it afterwards: stream-ordered free)
+    if norm_out is None:
+        norm_out = torch.empty(4, dtype=torch.float32, device=table.device)
+    _chk(norm_out, torch.float32, "norm_out")
+    _chk(per_tensor_norms, torch.float32, "per_tensor_norms")
+    assert norm_out.numel() >= 4 and norm_out.is_contiguous() and (per_tensor_norms is None or per_tensor_norms.numel() >= n_t)
+    _grad_norm_launch(table, n_t, blk, numel, grad_scale, max_grad_norm, norm_out, per_tensor_norms, found_inf)
+    _call("vpt_adam_step_multi_clip", dict(bytes=28.0 * numel), ptr(table), n_t, blk, *hyper, ptr(norm_out[1:]), _stream())
+    return table   # (norm_out too outlives the enqueue: the Adam launch reads norm_out[1] on the device; a scratch one is freed in stream order)
 
 
 def grads_nonfinite(grads):
     """int32 [1] device flag: 1 if any element of the fp32 tensors in `grads` is inf / nan (vpt_grads_nonfinite_multi, one launch; what
     torch.cuda.amp.GradScaler.unscale_ computes).  No host synchronisation here: the caller reads the flag when it needs it."""
-    import numpy as np
     grads = [g if g.is_contiguous() else g.contiguous() for g in grads if g is not None and g.numel()]
     if not grads:
         raise ValueError("grads_nonfinite: no gradient tensors to check")
     flag = torch.zeros(1, dtype=torch.int32, device=grads[0].device)
-    rec = np.zeros(len(grads), dtype=[("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<u8"), ("fb", "<i8")])
-    blk = 0
-    for i, g in enumerate(grads):
-        _chk(g, torch.float32, "grad")
-        rec[i] = (0, g.data_ptr(), 0, 0, g.numel(), blk)
-        blk += (g.numel() + 1023) // 1024
-    table = torch.from_numpy(rec.view(np.uint8)).to(grads[0].device, non_blocking=False)
-    _call("vpt_grads_nonfinite_multi", dict(bytes=4.0 * sum(g.numel() for g in grads)), ptr(table), len(grads), blk, ptr(flag), _stream())
+    table, blk, numel = _adam_table(grads)
+    _call("vpt_grads_nonfinite_multi", dict(bytes=4.0 * numel), ptr(table), len(grads), blk, ptr(flag), _stream())
     return flag
 
 

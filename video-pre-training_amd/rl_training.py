@@ -33,7 +33,8 @@ class PPOTrainer(BCTrainer):
         normalize_advantages: (A - mean) / (std + 1e-8) over the weighted frames of the call (the population std).
         update_value_normalizer: every loss_and_grads / step first feeds its value targets to the value head's EWMA normaliser, as the reference's
         ScaledMSEHead.loss does in training mode (lib/scaled_mse_head.py:43 -> lib/normalize_ewma.py:37-52), then normalises with the new statistics.
-        bc_kwargs: BCTrainer's arguments (lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, episode_starts).
+        bc_kwargs: BCTrainer's arguments (lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, episode_starts,
+        max_grad_norm -- global-norm gradient clipping, off by default; see there).
         The value head's Linear trains here (BCTrainer excludes it: it has no gradient under the BC loss)."""
         super().__init__(policy, **bc_kwargs)
         self.clip, self.kl_coef, self.entropy_coef, self.value_coef = float(clip), float(kl_coef), float(entropy_coef), float(value_coef)
@@ -198,26 +199,10 @@ class PPOTrainer(BCTrainer):
     @torch.no_grad()
     def step(self, img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target, *, prior_lp=None, frame_weight=None,
              metrics: Optional[dict] = None):
-        """One optimiser step on a [B, T] chunk.  Returns (loss, state_out).  The Adam launch and the loss-scale bookkeeping are BCTrainer.step's."""
+        """One optimiser step on a [B, T] chunk.  Returns (loss, state_out).  The Adam launch, the optional gradient-norm clip and the loss-scale
+        bookkeeping are BCTrainer.step's (CnnTrainingMixin._optimizer_tail; metrics gains grad_norm / clip_coef / grad_norm_per_tensor when max_grad_norm is set)."""
         self._need_optimizer_state()
         loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target,
                                                      prior_lp=prior_lp, frame_weight=frame_weight, metrics=metrics, unscaled=False)
-        names = [n for n in self.trainable if n in grads]
-        found_inf = torch.zeros(1, dtype=torch.int32, device=img_u8.device) if self.scaled else None
-        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
-                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
-                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                             grad_scale=self.grad_unscale(self._global_frames), found_inf=found_inf)
-        loss = float(loss)                     # (synchronises: the flag below is ready)
-        if self.scaled and int(found_inf.item()):
-            self.skipped_steps += 1
-            self._clean_steps = 0
-            self.loss_scale = max(self.loss_scale * 0.5, 1.0)
-            return loss, state_out
-        self.step_count += 1
-        if self.scaled:
-            self._clean_steps += 1
-            if self._clean_steps >= self.scale_growth_interval:
-                self._clean_steps, self.loss_scale = 0, min(self.loss_scale * 2.0, 65536.0)
-        self.policy._packed_key = None  # weights changed: re-pack before the next forward
+        loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._global_frames), img_u8.device, metrics)
         return loss, state_out

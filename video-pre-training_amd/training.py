@@ -2,8 +2,9 @@
 
     loss = -mean_{b,t}[ log pi(buttons_bt) + log pi(camera_bt) ]      (lib/action_head.py:176-184,252-253)
     th.optim.Adam(lr=1.81e-4, weight_decay=0.039428)                   (behavioural_cloning.py:38-40,63-67)
-    gradient clipping: none -- the reference's clip_grad_norm_ receives an exhausted generator and is a no-op
-                       (behavioural_cloning.py:60,63,121; SURVEY.md §2 'latent bugs'); reproduced, i.e. NOT applied
+    gradient clipping: none by default -- the reference's clip_grad_norm_ receives an exhausted generator and is a no-op
+                       (behavioural_cloning.py:60,63,121; SURVEY.md §2 'latent bugs'); BCTrainer(max_grad_norm=5.0) applies what the
+                       script meant, on the device (ops.grad_norm's launches + the coefficient inside the Adam launch)
     state: the KV memory is carried between chunks detached (behavioural_cloning.py:111)
 
 Every layer's backward runs on the HIP kernels: both action heads, final_ln, lastlayer, the four transformer blocks
@@ -58,8 +59,14 @@ def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], wei
 class BCTrainer(CnnTrainingMixin):
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  train_cnn: bool = True, optimizer_state: bool = True, loss_scale: Optional[float] = None,
-                 scale_growth_interval: int = 200, episode_starts: str = "chunk"):
-        """episode_starts: "chunk" (default: first[:, 0] only) or "frame": `first` honoured at every frame of the chunk, forward and backward,
+                 scale_growth_interval: int = 200, episode_starts: str = "chunk", max_grad_norm: Optional[float] = None):
+        """max_grad_norm: None (default: no clipping -- the reference's actual behaviour, its clip_grad_norm_ call receives an exhausted generator),
+        5.0 (MAX_GRAD_NORM, what behavioural_cloning.py:38-40,121 meant) or float("inf") (measure the norm, never clip).  When set, step() takes the
+        global l2 norm of the gradients of the mean loss on the device -- after the all-reduce, un-scaled: neither fp16's loss scale nor 1 / frames
+        reaches the threshold -- and the Adam launch multiplies by torch's clip coefficient; `metrics` gains grad_norm, clip_coef and
+        grad_norm_per_tensor, `last_grad_norm` keeps the norm.  A non-finite norm SKIPS the step on the device in both operand formats
+        (skipped_steps; fp16 also halves its loss scale) where torch would write NaN into every parameter (CnnTrainingMixin._optimizer_tail).
+        episode_starts: "chunk" (default: first[:, 0] only) or "frame": `first` honoured at every frame of the chunk, forward and backward,
         so that chunks cut from a stream of recordings of arbitrary length (sequence_batcher.SequenceBatcher) train as the reference's
         frame-by-frame loop does (behavioural_cloning.py:95-112).
         train_cnn=True (default, as the reference: behavioural_cloning.py:57-63 optimises policy.parameters(), i.e. every
@@ -74,6 +81,7 @@ class BCTrainer(CnnTrainingMixin):
         torch.cuda.amp.GradScaler: vpt_grads_nonfinite_multi checks the (all-reduced) gradients; an overflowed step is skipped on
         the device (the Adam launch reads the flag) and the scale halves, it doubles after `scale_growth_interval` clean steps."""
         self.train_cnn = bool(train_cnn)
+        self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
         self.episode_starts = check_episode_starts(episode_starts)
         self.policy = policy
         self.engine = policy._engine
@@ -111,7 +119,8 @@ class BCTrainer(CnnTrainingMixin):
         latter): Adam moments keyed by the reference's parameter names, the step count and the hyper-parameters."""
         self._need_optimizer_state()
         return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
-                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, exp_avg={n: t.detach().clone() for n, t in self.m.items()},
+                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
+                    exp_avg={n: t.detach().clone() for n, t in self.m.items()},
                     exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
 
     def _need_optimizer_state(self):
@@ -122,6 +131,8 @@ class BCTrainer(CnnTrainingMixin):
         self._need_optimizer_state()
         if self.scaled and "loss_scale" in sd:
             self.loss_scale = float(sd["loss_scale"])
+        if "max_grad_norm" in sd:           # (dicts written before the key existed keep the constructor's value)
+            self.max_grad_norm = self._checked_max_grad_norm(sd["max_grad_norm"])
         if set(sd["exp_avg"]) != set(self.m):
             raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
         self.step_count = int(sd["step"])
@@ -594,26 +605,8 @@ class BCTrainer(CnnTrainingMixin):
             loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera)
         else:
             loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, frame_weight=frame_weight, metrics=metrics)
-        names = [n for n in self.trainable if n in grads]
-        found_inf = torch.zeros(1, dtype=torch.int32, device=img_u8.device) if self.scaled else None
-        # one launch for all tensors (th.optim.Adam(policy.parameters()).step(), behavioural_cloning.py:122); in the fp16 mode it
-        # un-scales the gradients and is a no-op on the device when the overflow check (same table, one launch before) fired
-        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
-                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
-                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                             grad_scale=self.grad_unscale(self._global_frames), found_inf=found_inf)
-        loss = float(loss)                     # (synchronises: the flag below is ready)
-        if self.scaled and int(found_inf.item()):
-            self.skipped_steps += 1            # the ranks agree: every rank checked the same all-reduced gradients
-            self._clean_steps = 0
-            self.loss_scale = max(self.loss_scale * 0.5, 1.0)
-            return loss, state_out
-        self.step_count += 1
-        if self.scaled:
-            self._clean_steps += 1
-            if self._clean_steps >= self.scale_growth_interval:
-                self._clean_steps, self.loss_scale = 0, min(self.loss_scale * 2.0, 65536.0)
-        self.policy._packed_key = None  # weights changed: re-pack before the next forward
+        # the Adam launch (clipped when max_grad_norm is set) after the exchange: the norm is that of the summed global gradients, the same bits on every rank
+        loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._global_frames), img_u8.device, metrics)
         return loss, state_out
 
 
