@@ -29,59 +29,6 @@ class CnnTrainingMixin:
         self.fold_n_backward0 = os.environ.get("VPT_BC_FOLD_N_BWD0", "1") != "0"
 
     # ------------------------------------------------------------------------------------------
-    # The optimiser tail of every trainer's step(): ONE copy of the Adam launch, gradient-norm clipping and the loss-scale bookkeeping.
-    # ------------------------------------------------------------------------------------------
-    max_grad_norm = None         # None: no clipping (what the reference's script does); 5.0: what it meant; float("inf"): measure, never clip
-    last_grad_norm = None        # fp32 device scalar of the last step that measured (max_grad_norm set)
-
-    @staticmethod
-    def _checked_max_grad_norm(max_grad_norm):
-        if max_grad_norm is None:
-            return None
-        v = float(max_grad_norm)
-        if not v > 0:
-            raise ValueError(f"max_grad_norm must be positive (float('inf'): measure only) or None, got {max_grad_norm!r}")
-        return v
-
-    def _optimizer_tail(self, loss, grads, grad_scale: float, device, metrics=None):
-        """The Adam launch for every trainable tensor of `grads` + the bookkeeping -> (float(loss), skipped).  A class that mixes this in provides
-        params, trainable, m, v, step_count, lr / wd / betas / eps, scaled, loss_scale, scale_growth_interval, _clean_steps, skipped_steps, policy.
-        One launch for all tensors (th.optim.Adam(policy.parameters()).step(), behavioural_cloning.py:122); in the fp16 mode it un-scales the
-        gradients and is a no-op on the device when the overflow check (same table, one launch before) fired.
-        max_grad_norm set (clip_grad_norm_ as behavioural_cloning.py:121 meant it): the norm of grads * grad_scale -- the gradients of the MEAN loss,
-        after the all-reduce, whatever the loss scale -- is taken over the same table (that launch replaces the overflow check), the Adam launch
-        multiplies by the clip coefficient on the device.  A non-finite norm skips the step on the device in BOTH formats (skipped_steps counts it;
-        fp16 also halves its loss scale): torch.nn.utils.clip_grad_norm_ would instead write NaN into every parameter -- a deliberate difference.
-        `metrics` (when given and max_grad_norm is set) gains grad_norm, clip_coef and grad_norm_per_tensor {name: norm}: device tensors."""
-        names = [n for n in self.trainable if n in grads]
-        clip = self.max_grad_norm is not None
-        found_inf = torch.zeros(1, dtype=torch.int32, device=device) if (self.scaled or clip) else None
-        per = torch.empty(len(names), dtype=torch.float32, device=device) if (clip and metrics is not None) else None
-        norm_out = torch.empty(4, dtype=torch.float32, device=device) if clip else None
-        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
-                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
-                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                             grad_scale=grad_scale, found_inf=found_inf, max_grad_norm=self.max_grad_norm, norm_out=norm_out, per_tensor_norms=per)
-        if clip and names:
-            self.last_grad_norm = norm_out[0]
-            if metrics is not None:
-                metrics.update(grad_norm=norm_out[0], clip_coef=norm_out[1], grad_norm_per_tensor={n: per[i] for i, n in enumerate(names)})
-        loss = float(loss)                     # (synchronises: the flag below is ready)
-        if found_inf is not None and int(found_inf.item()):
-            self.skipped_steps += 1            # data-parallel: the ranks agree, every rank checked the same all-reduced gradients
-            if self.scaled:
-                self._clean_steps = 0
-                self.loss_scale = max(self.loss_scale * 0.5, 1.0)
-            return loss, True
-        self.step_count += 1
-        if self.scaled:
-            self._clean_steps += 1
-            if self._clean_steps >= self.scale_growth_interval:
-                self._clean_steps, self.loss_scale = 0, min(self.loss_scale * 2.0, 65536.0)
-        self.policy._packed_key = None  # weights changed (in place, behind autograd's version counters): re-pack before the next forward
-        return loss, False
-
-    # ------------------------------------------------------------------------------------------
     # IMPALA CNN: forward that keeps every activation (6.2 MB / frame on the 2x model: a 64 x 128 batch is 50 GB of
     # the 288 GB HBM, so nothing is recomputed), and the backward through the folded GroupNorm convolutions.
     # ------------------------------------------------------------------------------------------

@@ -116,10 +116,10 @@ class PPOTrainer(BCTrainer):
         std = ((w * (a - mean) ** 2).sum() / wsum).sqrt()
         return torch.where(live, (a - mean) / (std + 1e-8), torch.zeros_like(a))
 
-    def _value_norm(self, target, w):
+    def _value_norm(self, target, w, update: bool = True):
         """The optional normaliser update, then (mean, std) as a device pair: torch ops on the buffers, no host transfer."""
         nrm = self.policy.value_head.normalizer
-        if self.update_value_normalizer:
+        if update and self.update_value_normalizer:
             nrm.update(target.reshape(-1, *nrm.running_mean.shape), weight=w)
         mean, var = nrm.running_mean_var()
         return torch.stack([mean.reshape(-1)[0], torch.sqrt(var).reshape(-1)[0]]).to(torch.float32).contiguous()
@@ -170,9 +170,7 @@ class PPOTrainer(BCTrainer):
             self._fill_rl_metrics(metrics, totals, frame_out, S["bsz"], S["t"])
         g = self.backward_from(S, dz, value_grads=True)
         if unscaled and self.scaled:
-            fac = self.grad_unscale(self._global_frames)
-            for t_ in g.values():
-                t_.mul_(fac)
+            self._unscale_(g, self._global_frames)
         return loss, g, S["state_out"]
 
     @torch.no_grad()
@@ -186,8 +184,7 @@ class PPOTrainer(BCTrainer):
         m = bsz * t
         out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
         lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
-        mean, var = self.policy.value_head.normalizer.running_mean_var()
-        vnorm = torch.stack([mean.reshape(-1)[0], torch.sqrt(var).reshape(-1)[0]]).to(torch.float32).contiguous()
+        vnorm = self._value_norm(f["target"], f["w"], update=False)
         _, frame_out, totals = ops.rl_loss(lp_b, lp_c, f["ab"], f["ac"], f["old"], f["adv"], 0, 0.0, prior_buttons=f["qb"], prior_camera=f["qc"],
                                            value=out["vpred"].reshape(m), value_target=f["target"], vnorm=vnorm, weight=f["w"], clip=self.clip,
                                            kl_coef=self.kl_coef, entropy_coef=self.entropy_coef, value_coef=self.value_coef,
@@ -200,7 +197,7 @@ class PPOTrainer(BCTrainer):
     def step(self, img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target, *, prior_lp=None, frame_weight=None,
              metrics: Optional[dict] = None):
         """One optimiser step on a [B, T] chunk.  Returns (loss, state_out).  The Adam launch, the optional gradient-norm clip and the loss-scale
-        bookkeeping are BCTrainer.step's (CnnTrainingMixin._optimizer_tail; metrics gains grad_norm / clip_coef / grad_norm_per_tensor when max_grad_norm is set)."""
+        bookkeeping are BCTrainer.step's (TrainerBase._optimizer_tail; metrics gains grad_norm / clip_coef / grad_norm_per_tensor when max_grad_norm is set)."""
         self._need_optimizer_state()
         loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target,
                                                      prior_lp=prior_lp, frame_weight=frame_weight, metrics=metrics, unscaled=False)

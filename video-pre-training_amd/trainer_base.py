@@ -1,0 +1,337 @@
+"""What BCTrainer, PPOTrainer and IDMTrainer share behind the CNN (ONE copy each): the optimiser state and its checkpoint, the frame-weight check and
+the record-based loss, the fp16 un-scaling, the optimiser tail of step(), and the trunk -- its saving forward from the dense layer's output `d` to
+`x_trunk`, and its backward from the head logits' gradient down to `dd` = d loss / d `d`.
+
+The two trunks differ in five places, each a class attribute or a hook of TrainerBase:
+    attention        _attention_backward (BC: the masked kernel + the b_nd gradient; IDM: the mask-"none" kernel), the `attend` argument of the forward
+    fused_qkv        "qkvr": r_layer sits in the fused projection, its gradients come out of that GEMM's wgrad and bias sum; "qkv": r_layer is unreached
+    head_params      the rows of the fused head matrix (BC: buttons, camera, value; IDM: buttons, camera)
+    has_lastlayer    net.lastlayer between x_trunk and final_ln (BC)
+    final_ln_relu    final_ln reads relu(x_trunk) (IDM)
+The CNN's part of either pass stays with cnn_training.CnnTrainingMixin and the trainers' own chunk loops."""
+from typing import Dict, List, Optional
+
+import torch
+
+from . import ops
+from .cnn_training import CnnTrainingMixin
+
+
+def _round_up(x: int, m: int) -> int:
+    return (x + m - 1) // m * m
+
+
+def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], weight: torch.Tensor, need_dx: bool = True,
+                    res: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                    dx_f32: bool = True, dx_bf16_ld: Optional[int] = None, need_dw: bool = True):
+    """Backward of y = x W^T on the MFMA GEMM kernel.
+    dy16: bf16 [M, Np] (Np >= n, Np % 64 == 0, padding zero); x16: bf16 [M, K]; weight fp32 [n, K].
+    Returns (dx fp32 or None, dx bf16 or None, dW fp32 [n, K] or None).
+    dgrad:  dx = dy W      -> GEMM(A = dy, weights = W^T packed), optional ReLU gate `mask` and skip-sum `res`;
+    wgrad:  dW = dy^T x    -> the TN GEMM (ops.linear_wgrad): both operands row-major over the M frames, no transposes."""
+    np_ = dy16.shape[1]
+    k = weight.shape[1]
+    dx32 = dx16 = dw = None
+    if need_dx:   # W^T packed straight from the fp32 master by one kernel (was: zero, transpose, cast, permute -- four tensor ops)
+        wt = ops.pack_linear(weight.contiguous(), transposed=True, k_pad=np_, dtype=dy16.dtype)
+        dx32, dx16 = ops.linear(dy16, wt, k, res=res, mask=mask, out_f32=dx_f32,
+                                out_bf16=dx_bf16_ld is not None, out_bf16_ld=dx_bf16_ld)
+        del wt
+    if need_dw:       # dW = dy^T x straight from the row-major activations (vpt_gemm_tn_kernel: LDS transpose reads, no copies)
+        dw = ops.linear_wgrad(dy16, x16, np_)[:n]
+    return dx32, dx16, dw
+
+
+class TrainerBase(CnnTrainingMixin):
+    fused_qkv = "qkvr"           # the fused projection's name in the engine's packed weights and in saved[l]; "qkv": without r_layer (mask "none")
+    head_params = ("pi_head.buttons.linear_layer", "pi_head.camera.linear_layer", "value_head.linear")      # the fused head matrix, row blocks in order
+    has_lastlayer = True         # net.lastlayer between the blocks and final_ln
+    final_ln_relu = False        # final_ln reads relu(its input)
+    max_grad_norm = None         # None: no clipping (what the reference's script does); 5.0: what it meant; float("inf"): measure, never clip
+    last_grad_norm = None        # fp32 device scalar of the last step that measured (max_grad_norm set)
+
+    def _init_trainer(self, policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm):
+        """The state every trainer keeps (the constructors' docstrings say what the arguments mean)."""
+        self.train_cnn = bool(train_cnn)
+        self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
+        self.policy = policy
+        self.engine = policy._engine
+        self.dtype = self.engine.dtype
+        self.scaled = self.engine.precision == "fp16"
+        self.loss_scale = float(loss_scale) if loss_scale is not None else (256.0 if self.scaled else 1.0)
+        self.scale_growth_interval, self._clean_steps, self.skipped_steps = int(scale_growth_interval), 0, 0
+        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
+        self.step_count = 0
+        self._cnn_flags_from_env()       # gated_dgrad, fused_pool, fold_n_backward, fold_n_backward0 (cnn_training.py)
+        self.params: Dict[str, torch.nn.Parameter] = dict(policy.named_parameters())
+        self.trainable = [n for n in self.params if self._is_trainable(n)]
+        self.m = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
+        self.v = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
+
+    def _is_trainable(self, name: str) -> bool:
+        raise NotImplementedError
+
+    @staticmethod
+    def _checked_max_grad_norm(max_grad_norm):
+        if max_grad_norm is None:
+            return None
+        v = float(max_grad_norm)
+        if not v > 0:
+            raise ValueError(f"max_grad_norm must be positive (float('inf'): measure only) or None, got {max_grad_norm!r}")
+        return v
+
+    # ---- checkpoint / resume ---------------------------------------------------
+    def state_dict(self) -> dict:
+        """Optimizer state next to the policy's own `.weights` state_dict (behavioural_cloning.py:131-132 saves only the
+        latter): Adam moments keyed by the reference's parameter names, the step count and the hyper-parameters."""
+        self._need_optimizer_state()
+        return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
+                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
+                    exp_avg={n: t.detach().clone() for n, t in self.m.items()},
+                    exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
+
+    def _need_optimizer_state(self):
+        if not self.m and self.trainable:
+            raise RuntimeError(f"this {type(self).__name__} was built with optimizer_state=False (gradients only): step / state_dict / load_state_dict need the Adam moments")
+
+    def load_state_dict(self, sd: dict):
+        self._need_optimizer_state()
+        if self.scaled and "loss_scale" in sd:
+            self.loss_scale = float(sd["loss_scale"])
+        if "max_grad_norm" in sd:           # (dicts written before the key existed keep the constructor's value)
+            self.max_grad_norm = self._checked_max_grad_norm(sd["max_grad_norm"])
+        if set(sd["exp_avg"]) != set(self.m):
+            raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
+        self.step_count = int(sd["step"])
+        self.lr, self.wd, self.betas, self.eps = sd["lr"], sd["weight_decay"], tuple(sd["betas"]), sd["eps"]
+        for n in self.m:
+            self.m[n].copy_(sd["exp_avg"][n])
+            self.v[n].copy_(sd["exp_avg_sq"][n])
+
+    # ---- fp16 loss scaling ------------------------------------------------------------------------
+    def grad_unscale(self, global_frames: float) -> float:
+        """What loss_and_grads(unscaled=False)'s gradients must be multiplied by to be d(mean loss)/d(parameter): 1 in bf16.  (global_frames: the
+        global weight sum when the step carries frame weights.)"""
+        return 1.0 / (self.loss_scale * global_frames) if self.scaled else 1.0
+
+    def _unscale_(self, g: Dict[str, torch.Tensor], global_frames: float):
+        """loss_and_grads(unscaled=True) in the fp16 mode: the loss-scaled gradients -> those of the mean loss, in place."""
+        f = self.grad_unscale(global_frames)
+        for t_ in g.values():
+            t_.mul_(f)
+
+    # ---- frame weights, the loss and the metrics from the loss kernels' records ----------------------
+    @staticmethod
+    def _weights_on_device(frame_weight, img_u8):
+        """[B, T] weights -> (fp32 [M] on the images' device, [their fp64 sum, their fp64 minimum] as device scalars for the caller's ONE host transfer)."""
+        m = img_u8.shape[0] * img_u8.shape[1]
+        w = torch.as_tensor(frame_weight)
+        if w.numel() != m:
+            raise ValueError(f"frame_weight must hold one weight per frame ([{img_u8.shape[0]}, {img_u8.shape[1]}]), got {tuple(w.shape)}")
+        w = w.reshape(m).to(device=img_u8.device, dtype=torch.float32).contiguous()
+        w64 = w.to(torch.float64)
+        return w, [w64.sum(), w64.min()]
+
+    @staticmethod
+    def _check_weight_probe(wsum: float, wmin: float):
+        """The host half: a negative or non-finite weight raises ValueError (a NaN makes the minimum NaN, an infinity the sum infinite)."""
+        if not (wmin >= 0.0) or wsum != wsum or wsum in (float("inf"), float("-inf")):
+            raise ValueError(f"frame_weight must be finite and non-negative (min {wmin}, sum {wsum})")
+
+    @staticmethod
+    def _checked_weights(frame_weight, img_u8):
+        """[B, T] weights -> (fp32 [M] on the images' device, their fp64 sum as a host float).  The sum and the minimum come to the host in ONE
+        transfer; a negative or non-finite weight raises ValueError."""
+        w, probe = TrainerBase._weights_on_device(frame_weight, img_u8)
+        wsum, wmin = torch.stack(probe).tolist()
+        TrainerBase._check_weight_probe(wsum, wmin)
+        return w, wsum
+
+    @staticmethod
+    def _record_loss(frame_out, w, wsum):
+        """sum w nll / sum w of one rank from the kernel's per-frame records, in the ARITHMETIC OF THE DEFAULT PATH: per frame nll_b + nll_c (the
+        negated sum of the two picked log-probs, exactly), then torch's mean over the frames, then the factor M / sum w.  With every weight 1 each
+        step is the default path's own -- w x is x, the mean of the negated values is the negated mean, the factor is 1.0 -- so frame_weight=ones (and
+        metrics={} alone) returns the default path's loss bit for bit; the totals' fixed tree adds the same terms in another association and lands an
+        ulp away, which is why the returned loss is not read from them (they feed the metrics and the reduction over ranks).  M floats per step."""
+        nll = frame_out[:, 0] + frame_out[:, 1]
+        if w is None:
+            return nll.mean()
+        wn = torch.where(w != 0, w * nll, torch.zeros_like(nll))          # a zero-weight frame counts an exact zero whatever its record holds
+        return wn.mean() * (nll.numel() / wsum if wsum else float("nan"))
+
+    @staticmethod
+    def _fill_metrics(metrics: dict, totals, frame_out, bsz: int, t: int):
+        """totals [8] (ops.bc_loss's / ops.idm_loss's, or their sum over ranks) + this rank's records -> the metrics dict; device arithmetic only."""
+        ws = totals[6]
+        metrics.update(loss=(totals[0] + totals[1]) / ws, nll_buttons=totals[0] / ws, nll_camera=totals[1] / ws,
+                       entropy_buttons=totals[2] / ws, entropy_camera=totals[3] / ws, acc_buttons=totals[4] / ws, acc_camera=totals[5] / ws,
+                       weight_sum=ws, frames=totals[7])
+        if frame_out is not None:
+            metrics.update(frame_nll=(frame_out[:, 0] + frame_out[:, 1]).view(bsz, t), frame_out=frame_out.view(bsz, t, 8))
+
+    # ---- the optimiser tail of every trainer's step(): the Adam launch, gradient-norm clipping and the loss-scale bookkeeping --------------
+    def _optimizer_tail(self, loss, grads, grad_scale: float, device, metrics=None):
+        """The Adam launch for every trainable tensor of `grads` + the bookkeeping -> (float(loss), skipped).
+        One launch for all tensors (th.optim.Adam(policy.parameters()).step(), behavioural_cloning.py:122); in the fp16 mode it un-scales the
+        gradients and is a no-op on the device when the overflow check (same table, one launch before) fired.
+        max_grad_norm set (clip_grad_norm_ as behavioural_cloning.py:121 meant it): the norm of grads * grad_scale -- the gradients of the MEAN loss,
+        after the all-reduce, whatever the loss scale -- is taken over the same table (that launch replaces the overflow check), the Adam launch
+        multiplies by the clip coefficient on the device.  A non-finite norm skips the step on the device in BOTH formats (skipped_steps counts it;
+        fp16 also halves its loss scale): torch.nn.utils.clip_grad_norm_ would instead write NaN into every parameter -- a deliberate difference.
+        `metrics` (when given and max_grad_norm is set) gains grad_norm, clip_coef and grad_norm_per_tensor {name: norm}: device tensors."""
+        names = [n for n in self.trainable if n in grads]
+        clip = self.max_grad_norm is not None
+        found_inf = torch.zeros(1, dtype=torch.int32, device=device) if (self.scaled or clip) else None
+        per = torch.empty(len(names), dtype=torch.float32, device=device) if (clip and metrics is not None) else None
+        norm_out = torch.empty(4, dtype=torch.float32, device=device) if clip else None
+        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
+                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
+                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
+                             grad_scale=grad_scale, found_inf=found_inf, max_grad_norm=self.max_grad_norm, norm_out=norm_out, per_tensor_norms=per)
+        if clip and names:
+            self.last_grad_norm = norm_out[0]
+            if metrics is not None:
+                metrics.update(grad_norm=norm_out[0], clip_coef=norm_out[1], grad_norm_per_tensor={n: per[i] for i, n in enumerate(names)})
+        loss = float(loss)                     # (synchronises: the flag below is ready)
+        if found_inf is not None and int(found_inf.item()):
+            self.skipped_steps += 1            # data-parallel: the ranks agree, every rank checked the same all-reduced gradients
+            if self.scaled:
+                self._clean_steps = 0
+                self.loss_scale = max(self.loss_scale * 0.5, 1.0)
+            return loss, True
+        self.step_count += 1
+        if self.scaled:
+            self._clean_steps += 1
+            if self._clean_steps >= self.scale_growth_interval:
+                self._clean_steps, self.loss_scale = 0, min(self.loss_scale * 2.0, 65536.0)
+        self.policy._packed_key = None  # weights changed (in place, behind autograd's version counters): re-pack before the next forward
+        return loss, False
+
+    # ---- the trunk: ImgObsProcess.linear, pre_lstm_ln, the transformer blocks ------------------------------------------------------------
+    def _trunk_forward_saving(self, d: torch.Tensor, attend, **linear_kw) -> dict:
+        """d fp32 [M, 256] (the dense layer's pre-ReLU output) -> dict(dn, x_lin16, x_pre, saved, x_trunk): S's entries for the trunk, `saved` holding
+        per block what the backward reads.  attend(l, p, qkv) -> (att, the block's own saved entries) runs the attention of block l on the fused
+        projection's output.  linear_kw: `tiling` / `splitk` of every ops.linear here (none: the row count decides)."""
+        eng = self.engine
+        cfg, w, dt = eng.cfg, eng.w, self.dtype
+        hid, ratio = cfg["hidsize"], cfg["pointwise_ratio"]
+        pl, fq = "net.img_process.linear.", self.fused_qkv
+        _, dn = ops.layernorm(d, w[pl + "g"], w[pl + "b"], relu_in=True, dtype=dt)          # 16-bit
+        x, x_lin16 = ops.linear(dn, w[pl + "w"], hid, relu=True, out_f32=True, out_bf16=True, **linear_kw)
+        x_pre = None
+        if cfg["use_pre_lstm_ln"]:     # MinecraftPolicy.pre_lstm_ln (lib/policy.py:202-203)
+            x_pre = x
+            x, _ = ops.layernorm(x_pre, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=dt)
+        saved: List[dict] = []
+        for l in range(cfg["n_layers"]):
+            p = f"net.recurrent_layer.blocks.{l}."
+            x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=dt)
+            qkv, _ = ops.linear(x1b, w[p + fq + ".w"], eng.n_qkvr, bias=w[p + fq + ".b"], **linear_kw)
+            att, own = attend(l, p, qkv)
+            x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1, **linear_kw)      # x2 = x1 + proj (engine._block)
+            _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=dt)
+            _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True, **linear_kw)
+            xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, **linear_kw)
+            saved.append(dict(own, x=x, x1b=x1b, att=att, x2=x2, hb=hb, h2=h2, **{fq: qkv}))
+            x = xo
+        return dict(dn=dn, x_lin16=x_lin16, x_pre=x_pre, saved=saved, x_trunk=x)
+
+    def _attention_backward(self, S: dict, l: int, datt: torch.Tensor, g: Dict[str, torch.Tensor]) -> torch.Tensor:
+        """datt fp32 [M, hid] -> d loss / d (the fused projection's output of block l); adds to `g` what the attention itself trains."""
+        raise NotImplementedError
+
+    def _trunk_backward(self, S: dict, dz: torch.Tensor, P: Dict[str, torch.Tensor], value_grads: bool = False, debug: Optional[dict] = None):
+        """dz: 16-bit [M, ldz] = d loss / d (fused head logits) -> (g, dd): the gradient of every trainable tensor behind the CNN, and
+        dd fp32 [M, 256] = d loss / d (the dense layer's pre-activation output).  Launch order: heads (dgrad, wgrad, bias sums) -> final_ln ->
+        lastlayer (has_lastlayer) -> per block, last to first: mlp1, mlp0, its LayerNorm (+ skip), proj, _attention_backward, the fused projection's
+        GEMM (+ skip), pre_r_ln -> pre_lstm_ln -> ImgObsProcess.linear and its LayerNorm.  P: the parameters, detached.
+        value_grads: also return the value head's gradients (non-zero only when dz's value column is).  debug: a dict that receives clones of the
+        intermediate gradients (tools/bc_grad_diag.py)."""
+        cfg = self.engine.cfg
+        dev, saved, x_trunk = S["dev"], S["saved"], S["x_trunk"]
+        hid, ratio = cfg["hidsize"], cfg["pointwise_ratio"]
+        nq, r_fused = self.engine.n_qkvr, self.fused_qkv == "qkvr"
+        pl = "net.img_process.linear."
+        g: Dict[str, torch.Tensor] = {}
+        zeros = lambda n_: torch.zeros(n_, dtype=torch.float32, device=dev)
+        # heads (one fused GEMM over head_params' row blocks): dlat, dW, db
+        hw = [P[h + ".weight"] for h in self.head_params]
+        nb, nc = hw[0].shape[0], hw[1].shape[0]
+        wh = torch.cat(hw, 0)
+        nh = wh.shape[0]
+        dlat, _, dwh = linear_backward(dz, nh, S["lb"], wh)
+        if debug is not None:
+            debug['dlatent'] = dlat.clone(); debug['latent'] = S["lb"].float().clone()
+        dbh = zeros(nh)
+        ops.column_sum_(dbh, dz, nh)
+        g["pi_head.buttons.linear_layer.weight"], g["pi_head.camera.linear_layer.weight"] = dwh[:nb], dwh[nb:nb + nc]
+        g["pi_head.buttons.linear_layer.bias"], g["pi_head.camera.linear_layer.bias"] = dbh[:nb], dbh[nb:nb + nc]
+        if value_grads:
+            g["value_head.linear.weight"], g["value_head.linear.bias"] = dwh[nb + nc:nh].clone(), dbh[nb + nc:nh].clone()
+        del dz, dwh
+        # final_ln
+        g["net.final_ln.weight"], g["net.final_ln.bias"] = zeros(hid), zeros(hid)
+        dx = ops.layernorm_backward(S["y"] if self.has_lastlayer else x_trunk, P["net.final_ln.weight"], dlat, g["net.final_ln.weight"],
+                                    g["net.final_ln.bias"], relu_in=self.final_ln_relu)
+        del dlat
+        if self.has_lastlayer:      # y = relu(xb Wl^T); gate dy by y > 0 while casting to the GEMM operand
+            dy = dx
+            dy16 = ops.gate_cast(dy, hid, mask=S["y16"])
+            dxb, _, g["net.lastlayer.layer.weight"] = linear_backward(dy16, hid, S["xb"], P["net.lastlayer.layer.weight"])
+            g["net.lastlayer.norm.weight"], g["net.lastlayer.norm.bias"] = zeros(hid), zeros(hid)
+            dx = ops.layernorm_backward(x_trunk, P["net.lastlayer.norm.weight"], dxb, g["net.lastlayer.norm.weight"],
+                                        g["net.lastlayer.norm.bias"], relu_in=True)
+            if debug is not None:
+                debug['y'] = S["y"].clone(); debug['dy'] = dy.clone(); debug['dx_trunk'] = dx.clone(); debug['x_trunk'] = x_trunk.clone()
+            del dy, dy16, dxb
+        # transformer blocks, last to first
+        for l in reversed(range(cfg["n_layers"])):
+            p = f"net.recurrent_layer.blocks.{l}."
+            o = p + "r.orc_block."
+            s = saved[l]
+            dout16 = ops.gate_cast(dx, hid, dtype=self.dtype)
+            # mlp1: out = x2 + h2 W1^T + b1
+            _, dh16, g[p + "mlp1.layer.weight"] = linear_backward(dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"],
+                                                                  dx_f32=False, dx_bf16_ld=hid * ratio)
+            g[p + "mlp1.layer.bias"] = zeros(hid)
+            ops.column_sum_(g[p + "mlp1.layer.bias"], dout16, hid)
+            # mlp0: h2 = relu(hb W0^T)  (the ReLU gate was applied by the mask above)
+            dhb, _, g[p + "mlp0.layer.weight"] = linear_backward(dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"])
+            g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"] = zeros(hid), zeros(hid)
+            dx2 = ops.layernorm_backward(s["x2"], P[p + "mlp0.norm.weight"], dhb, g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"], dx_add=dx)
+            if debug is not None:
+                debug[f'dout16_{l}'] = dout16.clone(); debug[f'dh16_{l}'] = dh16.clone(); debug[f'dhb_{l}'] = dhb.clone()
+            del dh16, dhb, dout16
+            # proj: x2 = x1 + att Wp^T + bp
+            dx2_16 = ops.gate_cast(dx2, hid, dtype=self.dtype)
+            datt, _, g[o + "proj_layer.weight"] = linear_backward(dx2_16, hid, s["att"], P[o + "proj_layer.weight"])
+            g[o + "proj_layer.bias"] = zeros(hid)
+            ops.column_sum_(g[o + "proj_layer.bias"], dx2_16, hid)
+            # attention, then the fused projection: dx1 = dx2 (skip) + dqkv Wqkv
+            dqkv = self._attention_backward(S, l, datt, g)
+            dq16 = ops.gate_cast(dqkv, _round_up(nq, 64), dtype=self.dtype)
+            wq = torch.cat([P[f"{o}{c}_layer.weight"] for c in self.fused_qkv], 0)      # q_layer, k_layer, v_layer (, r_layer)
+            dx1, _, dwq = linear_backward(dq16, nq, s["x1b"], wq, res=dx2)
+            g[o + "q_layer.weight"], g[o + "k_layer.weight"], g[o + "v_layer.weight"] = dwq[:hid], dwq[hid:2 * hid], dwq[2 * hid:3 * hid]
+            # bias sums over the fused columns (k_layer and v_layer have none).  r_layer outside the fused projection is unreached: exact zeros
+            dbq = zeros(nq if r_fused else hid)
+            ops.column_sum_(dbq, dq16, dbq.numel())
+            g[o + "r_layer.weight"] = dwq[3 * hid:] if r_fused else torch.zeros_like(P[o + "r_layer.weight"])
+            g[o + "q_layer.bias"] = dbq[:hid]
+            g[o + "r_layer.bias"] = dbq[3 * hid:] if r_fused else torch.zeros_like(P[o + "r_layer.bias"])
+            g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"] = zeros(hid), zeros(hid)
+            dx = ops.layernorm_backward(s["x"], P[p + "pre_r_ln.weight"], dx1, g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"])
+            if debug is not None:
+                debug[f'dx_block{l}'] = dx.clone(); debug[f'dx2_block{l}'] = dx2.clone(); debug[f'datt{l}'] = datt.clone(); debug[f'dqkvr{l}'] = dqkv.clone()
+                debug[f'dx1_block{l}'] = dx1.clone(); debug[f'dq16_{l}'] = dq16.clone(); debug[f'dx2_16_{l}'] = dx2_16.clone()
+            del dx2, dx2_16, datt, dqkv, dq16, dx1, dwq
+        if cfg["use_pre_lstm_ln"]:
+            g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"] = zeros(hid), zeros(hid)
+            dx = ops.layernorm_backward(S["x_pre"], P["net.pre_lstm_ln.weight"], dx, g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"])
+        # ImgObsProcess.linear: x = relu(dn Wlin^T); its LayerNorm sits on relu(d), d being the CNN's output
+        dx16 = ops.gate_cast(dx, hid, mask=S["x_lin16"])
+        ddn, _, g[pl + "layer.weight"] = linear_backward(dx16, hid, S["dn"], P[pl + "layer.weight"])
+        g[pl + "norm.weight"], g[pl + "norm.bias"] = zeros(256), zeros(256)
+        dd = ops.layernorm_backward(S["d"], P[pl + "norm.weight"], ddn, g[pl + "norm.weight"], g[pl + "norm.bias"], relu_in=True)
+        return g, dd

@@ -19,44 +19,19 @@ gradients summed over RCCL in buckets -- trunk + heads while the CNN backward ru
 (BCTrainer.reduced_loss_and_grads); the 1 / global_frames factor is already in the loss gradient."""
 import contextlib
 import os
-from typing import Dict, List, Optional
+from typing import List, Optional
 
 import torch
 import torch.distributed as dist
 
 from . import distributed as D
-from . import ops, packing
-from .cnn_training import CnnTrainingMixin, _tap_sum, conv_param_grads  # noqa: F401  (conv_param_grads: this module's long-standing name for it)
+from . import ops
+from .cnn_training import _tap_sum, conv_param_grads  # noqa: F401  (conv_param_grads: this module's long-standing name for it)
 from .engine import DENSE_SPLITK, EpisodeMasks, check_episode_starts
+from .trainer_base import TrainerBase, _round_up, linear_backward  # noqa: F401  (linear_backward: this module's long-standing name for it)
 
 
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
-
-
-def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], weight: torch.Tensor, need_dx: bool = True,
-                    res: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
-                    dx_f32: bool = True, dx_bf16_ld: Optional[int] = None, need_dw: bool = True):
-    """Backward of y = x W^T on the MFMA GEMM kernel.
-    dy16: bf16 [M, Np] (Np >= n, Np % 64 == 0, padding zero); x16: bf16 [M, K]; weight fp32 [n, K].
-    Returns (dx fp32 or None, dx bf16 or None, dW fp32 [n, K] or None).
-    dgrad:  dx = dy W      -> GEMM(A = dy, weights = W^T packed), optional ReLU gate `mask` and skip-sum `res`;
-    wgrad:  dW = dy^T x    -> the TN GEMM (ops.linear_wgrad): both operands row-major over the M frames, no transposes."""
-    m, np_ = dy16.shape
-    k = weight.shape[1]
-    dev = dy16.device
-    dx32 = dx16 = dw = None
-    if need_dx:   # W^T packed straight from the fp32 master by one kernel (was: zero, transpose, cast, permute -- four tensor ops)
-        wt = ops.pack_linear(weight.contiguous(), transposed=True, k_pad=np_, dtype=dy16.dtype)
-        dx32, dx16 = ops.linear(dy16, wt, k, res=res, mask=mask, out_f32=dx_f32,
-                                out_bf16=dx_bf16_ld is not None, out_bf16_ld=dx_bf16_ld)
-        del wt
-    if need_dw:       # dW = dy^T x straight from the row-major activations (vpt_gemm_tn_kernel: LDS transpose reads, no copies)
-        dw = ops.linear_wgrad(dy16, x16, np_)[:n]
-    return dx32, dx16, dw
-
-
-class BCTrainer(CnnTrainingMixin):
+class BCTrainer(TrainerBase):
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  train_cnn: bool = True, optimizer_state: bool = True, loss_scale: Optional[float] = None,
                  scale_growth_interval: int = 200, episode_starts: str = "chunk", max_grad_norm: Optional[float] = None):
@@ -65,7 +40,7 @@ class BCTrainer(CnnTrainingMixin):
         global l2 norm of the gradients of the mean loss on the device -- after the all-reduce, un-scaled: neither fp16's loss scale nor 1 / frames
         reaches the threshold -- and the Adam launch multiplies by torch's clip coefficient; `metrics` gains grad_norm, clip_coef and
         grad_norm_per_tensor, `last_grad_norm` keeps the norm.  A non-finite norm SKIPS the step on the device in both operand formats
-        (skipped_steps; fp16 also halves its loss scale) where torch would write NaN into every parameter (CnnTrainingMixin._optimizer_tail).
+        (skipped_steps; fp16 also halves its loss scale) where torch would write NaN into every parameter (TrainerBase._optimizer_tail).
         episode_starts: "chunk" (default: first[:, 0] only) or "frame": `first` honoured at every frame of the chunk, forward and backward,
         so that chunks cut from a stream of recordings of arbitrary length (sequence_batcher.SequenceBatcher) train as the reference's
         frame-by-frame loop does (behavioural_cloning.py:95-112).
@@ -80,20 +55,11 @@ class BCTrainer(CnnTrainingMixin):
         1 / (loss_scale x global_frames).  `loss_scale` (default 256 for fp16, 1 = off for bf16) is dynamic as in
         torch.cuda.amp.GradScaler: vpt_grads_nonfinite_multi checks the (all-reduced) gradients; an overflowed step is skipped on
         the device (the Adam launch reads the flag) and the scale halves, it doubles after `scale_growth_interval` clean steps."""
-        self.train_cnn = bool(train_cnn)
-        self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
+        self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm)
         self.episode_starts = check_episode_starts(episode_starts)
-        self.policy = policy
-        self.engine = policy._engine
-        self.dtype = self.engine.dtype
-        self.scaled = self.engine.precision == "fp16"
-        self.loss_scale = float(loss_scale) if loss_scale is not None else (256.0 if self.scaled else 1.0)
-        self.scale_growth_interval, self._clean_steps, self.skipped_steps = int(scale_growth_interval), 0, 0
         # the autograd boundary's counterpart of loss_scale (lib/policy.py:_PolicyForwardFn.backward): where the largest incoming
         # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow it detects
         self.autograd_lift, self.autograd_overflows = 256.0, 0
-        self.lr, self.wd, self.betas, self.eps = lr, weight_decay, betas, eps
-        self.step_count = 0
         # Frame chunks of the CNN (forward-saving AND backward) alternate over this many HIP streams, chunk ci always on stream
         # ci % n: one chunk's HBM-bound passes (conv_backward_prepare, the affine backward, pool) and launch tails overlap the
         # other chunks' MFMA-bound convolutions, as in the inference engine.  Each stream accumulates its weight-gradient pieces in
@@ -104,42 +70,9 @@ class BCTrainer(CnnTrainingMixin):
         # bookkeeping.  The streams are created ONCE per trainer and only ever appended to (never replaced): the activations a
         # forward_saving() left for a later backward stay tied to the stream object that produced them.
         self.cnn_streams = int(os.environ.get("VPT_BC_STREAMS", self.engine.cnn_streams))
-        self._cnn_flags_from_env()       # gated_dgrad, fused_pool, fold_n_backward, fold_n_backward0 (cnn_training.py)
         self.force_exchange = os.environ.get("VPT_DP_FORCE_EXCHANGE", "0") == "1"      # see reduced_loss_and_grads
         self._arenas = None      # (key, (GradArena trunk + heads, GradArena CNN)) of the data-parallel step, built on first use
         self._streams: List[torch.cuda.Stream] = []
-        self.params: Dict[str, torch.nn.Parameter] = dict(policy.named_parameters())
-        self.trainable = [n for n in self.params if self._is_trainable(n)]
-        self.m = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
-        self.v = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
-
-    # ---- checkpoint / resume ---------------------------------------------------
-    def state_dict(self) -> dict:
-        """Optimizer state next to the policy's own `.weights` state_dict (behavioural_cloning.py:131-132 saves only the
-        latter): Adam moments keyed by the reference's parameter names, the step count and the hyper-parameters."""
-        self._need_optimizer_state()
-        return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
-                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
-                    exp_avg={n: t.detach().clone() for n, t in self.m.items()},
-                    exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
-
-    def _need_optimizer_state(self):
-        if not self.m and self.trainable:
-            raise RuntimeError("this BCTrainer was built with optimizer_state=False (gradients only): step / state_dict / load_state_dict need the Adam moments")
-
-    def load_state_dict(self, sd: dict):
-        self._need_optimizer_state()
-        if self.scaled and "loss_scale" in sd:
-            self.loss_scale = float(sd["loss_scale"])
-        if "max_grad_norm" in sd:           # (dicts written before the key existed keep the constructor's value)
-            self.max_grad_norm = self._checked_max_grad_norm(sd["max_grad_norm"])
-        if set(sd["exp_avg"]) != set(self.m):
-            raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
-        self.step_count = int(sd["step"])
-        self.lr, self.wd, self.betas, self.eps = sd["lr"], sd["weight_decay"], tuple(sd["betas"]), sd["eps"]
-        for n in self.m:
-            self.m[n].copy_(sd["exp_avg"][n])
-            self.v[n].copy_(sd["exp_avg_sq"][n])
 
     def _is_trainable(self, name: str) -> bool:
         if name.startswith("net.img_process.cnn.") and not self.train_cnn:
@@ -196,53 +129,8 @@ class BCTrainer(CnnTrainingMixin):
                 metrics["loss"] = loss
         g = self.backward_from(S, dz, on_trunk_grads=on_trunk_grads, debug=debug)
         if unscaled and self.scaled:
-            f = self.grad_unscale(gf)
-            for t_ in g.values():
-                t_.mul_(f)
+            self._unscale_(g, gf)
         return loss, g, S["state_out"]
-
-    def grad_unscale(self, global_frames: float) -> float:
-        """What loss_and_grads' gradients must be multiplied by to be d(mean loss)/d(parameter): 1 in bf16.  (global_frames: the global weight
-        sum when the step carries frame weights.)"""
-        return 1.0 / (self.loss_scale * global_frames) if self.scaled else 1.0
-
-    @staticmethod
-    def _checked_weights(frame_weight, img_u8):
-        """[B, T] weights -> (fp32 [M] on the images' device, their fp64 sum as a host float).  The sum and the minimum come to the host in ONE
-        transfer; a negative or non-finite weight raises ValueError (a NaN makes the minimum NaN, an infinity the sum infinite)."""
-        m = img_u8.shape[0] * img_u8.shape[1]
-        w = torch.as_tensor(frame_weight)
-        if w.numel() != m:
-            raise ValueError(f"frame_weight must hold one weight per frame ([{img_u8.shape[0]}, {img_u8.shape[1]}]), got {tuple(w.shape)}")
-        w = w.reshape(m).to(device=img_u8.device, dtype=torch.float32).contiguous()
-        w64 = w.to(torch.float64)
-        wsum, wmin = torch.stack([w64.sum(), w64.min()]).tolist()
-        if not (wmin >= 0.0) or wsum != wsum or wsum in (float("inf"), float("-inf")):
-            raise ValueError(f"frame_weight must be finite and non-negative (min {wmin}, sum {wsum})")
-        return w, wsum
-
-    @staticmethod
-    def _record_loss(frame_out, w, wsum):
-        """sum w nll / sum w of one rank from the kernel's per-frame records, in the ARITHMETIC OF THE DEFAULT PATH: per frame nll_b + nll_c (the
-        negated sum of the two picked log-probs, exactly), then torch's mean over the frames, then the factor M / sum w.  With every weight 1 each
-        step is the default path's own -- w x is x, the mean of the negated values is the negated mean, the factor is 1.0 -- so frame_weight=ones (and
-        metrics={} alone) returns the default path's loss bit for bit; the totals' fixed tree adds the same terms in another association and lands an
-        ulp away, which is why the returned loss is not read from them (they feed the metrics and the reduction over ranks).  M floats per step."""
-        nll = frame_out[:, 0] + frame_out[:, 1]
-        if w is None:
-            return nll.mean()
-        wn = torch.where(w != 0, w * nll, torch.zeros_like(nll))          # a zero-weight frame counts an exact zero whatever its record holds
-        return wn.mean() * (nll.numel() / wsum if wsum else float("nan"))
-
-    @staticmethod
-    def _fill_metrics(metrics: dict, totals, frame_out, bsz: int, t: int):
-        """totals [8] (ops.bc_loss's, or their sum over ranks) + this rank's records -> the metrics dict; device arithmetic only."""
-        ws = totals[6]
-        metrics.update(loss=(totals[0] + totals[1]) / ws, nll_buttons=totals[0] / ws, nll_camera=totals[1] / ws,
-                       entropy_buttons=totals[2] / ws, entropy_camera=totals[3] / ws, acc_buttons=totals[4] / ws, acc_camera=totals[5] / ws,
-                       weight_sum=ws, frames=totals[7])
-        if frame_out is not None:
-            metrics.update(frame_nll=(frame_out[:, 0] + frame_out[:, 1]).view(bsz, t), frame_out=frame_out.view(bsz, t, 8))
 
     @torch.no_grad()
     def evaluate(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None):
@@ -270,14 +158,13 @@ class BCTrainer(CnnTrainingMixin):
     def forward_saving(self, img_u8, first, state_in, mask: Optional[dict] = None) -> dict:
         """The policy forward with every activation the backward needs kept alive.  Returns the saved-state dict S:
         S["lp_b"] / S["lp_c"] fp32 [M, n] log-probs, S["logits"] fp32 [M, nb+nc+1] (last column: raw value), S["state_out"]."""
-        pol, eng = self.policy, self.engine
-        pol._ensure_packed()
+        eng = self.engine
+        self.policy._ensure_packed()
         cfg, w = eng.cfg, eng.w
         bsz, t = img_u8.shape[:2]
         m = bsz * t
-        hid, heads, maxlen = cfg["hidsize"], cfg["heads"], cfg["maxlen"]
-        ratio = cfg["pointwise_ratio"]
-        dev = img_u8.device
+        hid, heads = cfg["hidsize"], cfg["heads"]
+        dev, dt = img_u8.device, self.dtype
         nb, nc = eng.n_buttons, eng.n_camera
         frames = img_u8.reshape(m, *img_u8.shape[2:]).contiguous()
 
@@ -297,36 +184,21 @@ class BCTrainer(CnnTrainingMixin):
         for st in streams:
             main.wait_stream(st)
         d = outs[0] if len(outs) == 1 else torch.cat(outs, 0)                     # [M,256] pre-ReLU dense output
-        pl = "net.img_process.linear."
-        dt = self.dtype
-        _, dn = ops.layernorm(d, w[pl + "g"], w[pl + "b"], relu_in=True, dtype=dt)          # 16-bit
-        x, x16 = ops.linear(dn, w[pl + "w"], hid, relu=True, out_f32=True, out_bf16=True)
-        x_lin16 = x16
-        x_pre = None
-        if cfg["use_pre_lstm_ln"]:     # MinecraftPolicy.pre_lstm_ln (lib/policy.py:202-203)
-            x_pre = x
-            x, _ = ops.layernorm(x_pre, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=dt)
-        episodes = EpisodeMasks(first, bsz, t, maxlen, self.episode_starts)      # the bookkeeping of PolicyEngine.forward: the same memories
+        episodes = EpisodeMasks(first, bsz, t, cfg["maxlen"], self.episode_starts)      # the bookkeeping of PolicyEngine.forward: the same memories
         qlo = episodes.qlo
-        saved: List[dict] = []
         state_out = []
-        for l in range(cfg["n_layers"]):
-            p = f"net.recurrent_layer.blocks.{l}."
+
+        def attend(l, p, qkvr):
             state_mask, (kmem, vmem) = state_in[l]
             memvalid, new_mask = episodes.layer(state_mask, dev)
             kmem, vmem = kmem.contiguous(), vmem.contiguous()
-            x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=dt)
-            qkvr, _ = ops.linear(x1b, w[p + "qkvr.w"], eng.n_qkvr, bias=w[p + "qkvr.b"])
             att = ops.masked_attention(qkvr, kmem, vmem, memvalid, w[p + "b_nd"], bsz, t, heads, hid, dtype=dt, qlo=qlo)
             kout, vout = ops.kv_memory_update(qkvr, kmem, vmem, bsz, t, hid)
-            x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1)
-            _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=dt)
-            _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True)
-            xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2)
-            saved.append(dict(x=x, x1b=x1b, qkvr=qkvr, kmem=kmem, vmem=vmem, memvalid=memvalid, qlo=qlo, att=att, x2=x2, hb=hb, h2=h2))
             state_out.append((new_mask, (kout, vout)))
-            x = xo
-        x_trunk = x
+            return att, dict(kmem=kmem, vmem=vmem, memvalid=memvalid, qlo=qlo)
+
+        trunk = self._trunk_forward_saving(d, attend)       # no tiling / splitk: the row count decides ("auto"), part of this trainer's bits
+        x_trunk = trunk["x_trunk"]
         _, xb = ops.layernorm(x_trunk, w["last.g"], w["last.b"], relu_in=True, dtype=dt)
         y, y16 = ops.linear(xb, w["last.w"], hid, relu=True, out_f32=True, out_bf16=True)
         _, lb = ops.layernorm(y, w["final.g"], w["final.b"], dtype=dt)
@@ -336,105 +208,30 @@ class BCTrainer(CnnTrainingMixin):
               for h, n_ in (("buttons", nb), ("camera", nc))}
         lp_b = ops.log_softmax_cols(logits, 0, nb, temp, mask=mk["buttons"])
         lp_c = ops.log_softmax_cols(logits, nb, nc, temp, mask=mk["camera"])
-        return dict(m=m, bsz=bsz, t=t, dev=dev, d=d, dn=dn, x_lin16=x_lin16, x_pre=x_pre, saved=saved, x_trunk=x_trunk, xb=xb, y=y, y16=y16, lb=lb,
-                    logits=logits, lp_b=lp_b, lp_c=lp_c, cnn_saved=cnn_saved, state_out=state_out, ldz=_round_up(nb + nc + 1, 64), mask=mk)
+        return dict(trunk, m=m, bsz=bsz, t=t, dev=dev, d=d, xb=xb, y=y, y16=y16, lb=lb, logits=logits, lp_b=lp_b, lp_c=lp_c,
+                    cnn_saved=cnn_saved, state_out=state_out, ldz=_round_up(nb + nc + 1, 64), mask=mk)
+
+    def _attention_backward(self, S, l, datt, g):
+        """The masked attention's backward; the relative-position bias b_nd is trained by it."""
+        cfg = self.engine.cfg
+        p = f"net.recurrent_layer.blocks.{l}."
+        s = S["saved"][l]
+        db_nd = g[p + "r.orc_block.b_nd"] = torch.zeros(10, cfg["maxlen"], dtype=torch.float32, device=S["dev"])
+        return ops.masked_attention_backward(s["qkvr"], s["kmem"], s["vmem"], s["memvalid"], self.engine.w[p + "b_nd"], datt,
+                                             db_nd, S["bsz"], S["t"], cfg["heads"], cfg["hidsize"], qlo=s["qlo"])
 
     @torch.no_grad()
     def backward_from(self, S: dict, dz: torch.Tensor, on_trunk_grads=None, debug: Optional[dict] = None, value_grads: bool = False):
         """Backward of everything below the head logits.  dz: bf16 [M, ldz] = d loss / d (fused head logits).
         Consumes S (the CNN activations are released chunk by chunk).  value_grads: also return the value head's gradients
         (non-zero only when dz's value column is)."""
-        pol, eng = self.policy, self.engine
-        cfg, w = eng.cfg, eng.w
+        eng = self.engine
         P = {n: p.detach() for n, p in self.params.items()}
-        m, bsz, t, dev = S["m"], S["bsz"], S["t"], S["dev"]
-        hid, heads, maxlen = cfg["hidsize"], cfg["heads"], cfg["maxlen"]
-        ratio = cfg["pointwise_ratio"]
-        nb, nc = eng.n_buttons, eng.n_camera
-        d, dn, x_lin16, saved, x_trunk, xb, y, y16, lb = (S[k] for k in ("d", "dn", "x_lin16", "saved", "x_trunk", "xb", "y", "y16", "lb"))
-        cnn_saved = S["cnn_saved"]
-        pl = "net.img_process.linear."
-        g: Dict[str, torch.Tensor] = {}
-        zeros = lambda n_: torch.zeros(n_, dtype=torch.float32, device=dev)
-        nh = nb + nc + 1
-        # heads (fused [buttons; camera; value] GEMM): dlat, dW, db
-        wh = torch.cat([P["pi_head.buttons.linear_layer.weight"], P["pi_head.camera.linear_layer.weight"],
-                        P["value_head.linear.weight"]], 0)
-        dlat, _, dwh = linear_backward(dz, nh, lb, wh)
-        if debug is not None:
-            debug['dlatent'] = dlat.clone(); debug['latent'] = lb.float().clone(); debug['y'] = y.clone()
-        dbh = zeros(nh)
-        ops.column_sum_(dbh, dz, nh)
-        g["pi_head.buttons.linear_layer.weight"], g["pi_head.camera.linear_layer.weight"] = dwh[:nb], dwh[nb:nb + nc]
-        g["pi_head.buttons.linear_layer.bias"], g["pi_head.camera.linear_layer.bias"] = dbh[:nb], dbh[nb:nb + nc]
-        if value_grads:
-            g["value_head.linear.weight"], g["value_head.linear.bias"] = dwh[nb + nc:nh].clone(), dbh[nb + nc:nh].clone()
-        del dz, dwh
-        # final_ln
-        g["net.final_ln.weight"], g["net.final_ln.bias"] = zeros(hid), zeros(hid)
-        dy = ops.layernorm_backward(y, P["net.final_ln.weight"], dlat, g["net.final_ln.weight"], g["net.final_ln.bias"])
-        # lastlayer: y = relu(xb Wl^T); gate dy by y > 0 while casting to the GEMM operand
-        dy16 = ops.gate_cast(dy, hid, mask=y16)
-        dxb, _, g["net.lastlayer.layer.weight"] = linear_backward(dy16, hid, xb, P["net.lastlayer.layer.weight"])
-        g["net.lastlayer.norm.weight"], g["net.lastlayer.norm.bias"] = zeros(hid), zeros(hid)
-        dx = ops.layernorm_backward(x_trunk, P["net.lastlayer.norm.weight"], dxb, g["net.lastlayer.norm.weight"],
-                                    g["net.lastlayer.norm.bias"], relu_in=True)
-        if debug is not None:
-            debug['dy'] = dy.clone(); debug['dx_trunk'] = dx.clone(); debug['x_trunk'] = x_trunk.clone()
-        del dy, dy16, dxb, dlat
-        # transformer blocks, last to first
-        for l in reversed(range(cfg["n_layers"])):
-            p = f"net.recurrent_layer.blocks.{l}."
-            o = p + "r.orc_block."
-            s = saved[l]
-            dout16 = ops.gate_cast(dx, hid, dtype=self.dtype)
-            # mlp1: out = x2 + h2 W1^T + b1
-            _, dh16, g[p + "mlp1.layer.weight"] = linear_backward(dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"],
-                                                                  dx_f32=False, dx_bf16_ld=hid * ratio)
-            g[p + "mlp1.layer.bias"] = zeros(hid)
-            ops.column_sum_(g[p + "mlp1.layer.bias"], dout16, hid)
-            # mlp0: h2 = relu(hb W0^T)  (the ReLU gate was applied by the mask above)
-            dhb, _, g[p + "mlp0.layer.weight"] = linear_backward(dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"])
-            g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"] = zeros(hid), zeros(hid)
-            dx2 = ops.layernorm_backward(s["x2"], P[p + "mlp0.norm.weight"], dhb, g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"], dx_add=dx)
-            if debug is not None:
-                debug[f'dout16_{l}'] = dout16.clone(); debug[f'dh16_{l}'] = dh16.clone(); debug[f'dhb_{l}'] = dhb.clone()
-            del dh16, dhb, dout16
-            # proj: x2 = x1 + att Wp^T + bp
-            dx2_16 = ops.gate_cast(dx2, hid, dtype=self.dtype)
-            datt, _, g[o + "proj_layer.weight"] = linear_backward(dx2_16, hid, s["att"], P[o + "proj_layer.weight"])
-            g[o + "proj_layer.bias"] = zeros(hid)
-            ops.column_sum_(g[o + "proj_layer.bias"], dx2_16, hid)
-            # attention
-            g[o + "b_nd"] = torch.zeros(10, maxlen, dtype=torch.float32, device=dev)
-            dqkvr = ops.masked_attention_backward(s["qkvr"], s["kmem"], s["vmem"], s["memvalid"], w[p + "b_nd"], datt,
-                                                  g[o + "b_nd"], bsz, t, heads, hid, qlo=s["qlo"])
-            nq = eng.n_qkvr
-            dq16 = ops.gate_cast(dqkvr, _round_up(nq, 64), dtype=self.dtype)
-            wq = torch.cat([P[o + "q_layer.weight"], P[o + "k_layer.weight"], P[o + "v_layer.weight"], P[o + "r_layer.weight"]], 0)
-            dx1, _, dwq = linear_backward(dq16, nq, s["x1b"], wq, res=dx2)   # dx1 = dx2 (skip) + dqkvr Wqkvr
-            g[o + "q_layer.weight"], g[o + "k_layer.weight"] = dwq[:hid], dwq[hid:2 * hid]
-            g[o + "v_layer.weight"], g[o + "r_layer.weight"] = dwq[2 * hid:3 * hid], dwq[3 * hid:]
-            dbq = zeros(nq)
-            ops.column_sum_(dbq, dq16, nq)
-            g[o + "q_layer.bias"], g[o + "r_layer.bias"] = dbq[:hid], dbq[3 * hid:]
-            g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"] = zeros(hid), zeros(hid)
-            dx = ops.layernorm_backward(s["x"], P[p + "pre_r_ln.weight"], dx1, g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"])
-            if debug is not None:
-                debug[f'dx_block{l}'] = dx.clone(); debug[f'dx2_block{l}'] = dx2.clone(); debug[f'datt{l}'] = datt.clone(); debug[f'dqkvr{l}'] = dqkvr.clone()
-                debug[f'dx1_block{l}'] = dx1.clone(); debug[f'dq16_{l}'] = dq16.clone(); debug[f'dx2_16_{l}'] = dx2_16.clone()
-            del dx2, dx2_16, datt, dqkvr, dq16, dx1, dwq
-        if cfg["use_pre_lstm_ln"]:
-            g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"] = zeros(hid), zeros(hid)
-            dx = ops.layernorm_backward(S["x_pre"], P["net.pre_lstm_ln.weight"], dx, g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"])
-        # ImgObsProcess.linear: x = relu(dn Wlin^T)
-        dx16 = ops.gate_cast(dx, hid, mask=x_lin16)
-        ddn, _, g[pl + "layer.weight"] = linear_backward(dx16, hid, dn, P[pl + "layer.weight"])
-        g[pl + "norm.weight"], g[pl + "norm.bias"] = zeros(256), zeros(256)
-        dd = ops.layernorm_backward(d, P[pl + "norm.weight"], ddn, g[pl + "norm.weight"], g[pl + "norm.bias"], relu_in=True)
+        g, dd = self._trunk_backward(S, dz, P, value_grads=value_grads, debug=debug)
         if on_trunk_grads is not None:
             on_trunk_grads(g)
         if self.train_cnn:
+            m, cnn_saved = S["m"], S["cnn_saved"]
             acc = self._cnn_backward_begin(P)
             n_acc = max(1, min(self.cnn_streams, len(cnn_saved)))
             accs = [acc] + [self._cnn_backward_accumulators(acc) for _ in range(n_acc - 1)]     # operands shared, accumulators per stream
