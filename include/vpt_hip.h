@@ -380,6 +380,14 @@ int vpt_adam_step_multi_clip(const void* table, int ntensors, int64_t total_bloc
                              float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, const float* clip_coef,
                              void* stream);
 
+/* Gradient accumulation over micro-batches: param[i] = param[i] + grad[i] (one fp32 add) for every tensor of the SAME table as
+ * vpt_adam_step_multi, in one launch.  `param` names the fp32 accumulator (read and written), `grad` the addend (read only);
+ * exp_avg and exp_avg_sq are ignored.  No reductions and no atomics -- the same inputs give the same bits -- and no byte outside
+ * [param, param + n) is written.  inf / nan go through the sum: vpt_grads_nonfinite_multi / vpt_grad_norm_multi in front of the
+ * Adam launch see them.  An accumulator must not overlap its addend.  (torch.autograd sums .grad in the same way when backward()
+ * runs more than once before optimizer.step(); behavioural_cloning.py:117-122 takes one step per batch.) */
+int vpt_grad_accumulate_multi(const void* table, int ntensors, int64_t total_blocks, void* stream);
+
 /* ---- behavioural-cloning step: backward of the heads / trunk / transformer (the reference uses torch autograd,
  * behavioural_cloning.py:117-119).  Linear layers reuse vpt_linear_forward (dgrad: W^T packed; wgrad: A = dY^T). */
 

@@ -564,6 +564,12 @@ int vpt_grad_norm_multi(const void* table, int ntensors, int64_t total_blocks, f
                                     (int*)flag, (hipStream_t)stream), "vpt_grad_norm_multi");
 }
 
+int vpt_grad_accumulate_multi(const void* table, int ntensors, int64_t total_blocks, void* stream) {
+  if (!table && ntensors > 0) return fail(-1, "vpt_grad_accumulate_multi: null table");
+  if (ntensors < 0 || total_blocks < 0) return fail(-1, "vpt_grad_accumulate_multi: negative tensor / block count");
+  CHECK_LAUNCH(vpt_grad_accumulate_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, (hipStream_t)stream), "vpt_grad_accumulate_multi");
+}
+
 int vpt_grads_nonfinite_multi(const void* table, int ntensors, int64_t total_blocks, int32_t* flag, void* stream) {
   if ((!table && ntensors > 0) || !flag) return fail(-1, "vpt_grads_nonfinite_multi: null table / flag");
   CHECK_LAUNCH(vpt_grads_nonfinite_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, (int*)flag, (hipStream_t)stream), "vpt_grads_nonfinite_multi");

@@ -14,6 +14,9 @@
 //                                                                    reciprocal x scalar there); 1 when max_norm <= 0, 0 when total is not finite
 //   norm_out[2]  = total not finite
 // No float atomics, no "last workgroup" counters: every launch computes the same bits.  tests/grad_norm_ref.py restates all of it in numpy.
+//
+// Below the norm kernels, over the same table walk: vpt_grad_accumulate_kernel, the one-launch sum of a micro-batch's gradients into the window's
+// accumulators (gradient accumulation).
 #include "vpt_common.h"
 #include "vpt_kernels.h"
 
@@ -121,6 +124,66 @@ __global__ __launch_bounds__(256) void vpt_grad_norm_finish_kernel(const double*
   norm_out[2] = finite ? 0.0f : 1.0f;
   norm_out[3] = 0.0f;
   if (flag && !finite) *flag = 1;
+}
+
+// ---- gradient accumulation over micro-batches: p[i] = p[i] + g[i] for every tensor of the table in ONE launch (p: the fp32 accumulator, g: the
+// addend; m and v are not read).  The table walk and block mapping of the norm kernel above: VPT_GN_BLOCKS_PER_WG consecutive 1024-element blocks per
+// workgroup, all their 16-byte loads issued before the first store.  One fp32 add per element, no reductions, no atomics: the same inputs give the
+// same bits, inf / nan go through the sum (the norm launch / overflow check in front of the Adam launch sees them).  Only [p, p + n) is written.
+__global__ __launch_bounds__(256) void vpt_grad_accumulate_kernel(const VptAdamTensor* __restrict__ table, int ntensors, long total_blocks) {
+  const long b0 = (long)blockIdx.x * VPT_GN_BLOCKS_PER_WG;
+  const int tid = threadIdx.x;
+  float* tp[VPT_GN_BLOCKS_PER_WG];
+  size_t rem[VPT_GN_BLOCKS_PER_WG];        // elements of the tensor from this lane's first one on (0: nothing to do)
+  float a[VPT_GN_BLOCKS_PER_WG][4], g[VPT_GN_BLOCKS_PER_WG][4];
+#pragma unroll
+  for (int k = 0; k < VPT_GN_BLOCKS_PER_WG; ++k) {
+    tp[k] = nullptr; rem[k] = 0;
+    a[k][0] = a[k][1] = a[k][2] = a[k][3] = 0.f;
+    g[k][0] = g[k][1] = g[k][2] = g[k][3] = 0.f;
+    const long b = b0 + k;
+    if (b >= total_blocks) continue;       // uniform
+    int lo = 0, hi = ntensors - 1;
+    while (lo < hi) {   // last descriptor with first_block <= b
+      const int mid = (lo + hi + 1) >> 1;
+      if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
+    }
+    const size_t n = table[lo].n;
+    const size_t i0 = ((size_t)(b - table[lo].first_block) * 256 + tid) * 4;
+    if (i0 >= n) continue;
+    tp[k] = table[lo].p + i0;
+    rem[k] = n - i0;
+    const float* tg = table[lo].g + i0;
+    if (rem[k] >= 4) {   // views may start at any element: unaligned dwordx4 is legal on gfx950 (vpt_adam_multi_kernel)
+      const f32x4 va = *(const f32x4*)tp[k], vg = *(const f32x4*)tg;
+      a[k][0] = va.x; a[k][1] = va.y; a[k][2] = va.z; a[k][3] = va.w;
+      g[k][0] = vg.x; g[k][1] = vg.y; g[k][2] = vg.z; g[k][3] = vg.w;
+    } else {             // the tensor's last (partial) group of four
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if ((size_t)j < rem[k]) { a[k][j] = tp[k][j]; g[k][j] = tg[j]; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VPT_GN_BLOCKS_PER_WG; ++k) {
+    if (rem[k] >= 4) {
+      f32x4 s;
+      s.x = a[k][0] + g[k][0]; s.y = a[k][1] + g[k][1]; s.z = a[k][2] + g[k][2]; s.w = a[k][3] + g[k][3];
+      *(f32x4*)tp[k] = s;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 3; ++j)
+        if ((size_t)j < rem[k]) tp[k][j] = a[k][j] + g[k][j];
+    }
+  }
+}
+
+extern "C" int vpt_grad_accumulate_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, hipStream_t stream) {
+  if (ntensors <= 0 || total_blocks <= 0) return 0;
+  const long wgs = (total_blocks + VPT_GN_BLOCKS_PER_WG - 1) / VPT_GN_BLOCKS_PER_WG;
+  if (wgs > 0x7fffffffL) return -2;
+  hipLaunchKernelGGL(vpt_grad_accumulate_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, table_dev, ntensors, total_blocks);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 extern "C" long vpt_grad_norm_workspace_floats(int ntensors, long total_blocks) {

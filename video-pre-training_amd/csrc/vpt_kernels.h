@@ -481,6 +481,7 @@ int vpt_grads_nonfinite_launch(const VptAdamTensor* table_dev, int ntensors, lon
 long vpt_grad_norm_workspace_floats(int ntensors, long total_blocks);
 int vpt_grad_norm_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, float grad_scale, float max_norm, float* workspace,
                          float* norm_out, float* per_tensor, int* flag, hipStream_t s);
+int vpt_grad_accumulate_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, hipStream_t s);
 int vpt_affine_bwd_launch(const VptAffineBwdArgs* a, int pass, hipStream_t s);
 long vpt_affine_bwd_partial_floats(int frames, int CB, int HW, int per_element, int pass);
 int vpt_pool_bwd_launch(const VptPoolBwdArgs* a, hipStream_t s);

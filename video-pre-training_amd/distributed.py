@@ -109,6 +109,21 @@ class GradArena:
         if dst:
             torch._foreach_copy_(dst, src)
 
+    def accumulate(self, grads: dict) -> None:
+        """Add grads[name] to the arena for every name it holds (missing names add nothing) in ONE ops.grad_accumulate_ launch and re-point
+        grads[name] at the view: a later micro-batch of a gradient-accumulation window, after `adopt` took the first."""
+        from . import ops
+        dst, src = [], []
+        for n in self.names:
+            v = self.view(n)
+            g = grads.get(n)
+            if g is not None:
+                dst.append(v.view(-1))
+                src.append(g.contiguous().view(-1))
+            grads[n] = v
+        if dst:
+            ops.grad_accumulate_(dst, src)
+
     def all_reduce_start(self, force: bool = False):
         """Asynchronous in-place sum of every bucket; returns the work handles (wait() on each, or all_reduce_finish).
         force: issue the collectives in a one-rank group too (a test that the transport -- RCCL on a 1-GPU box -- takes the arena's slices)."""

@@ -79,10 +79,10 @@ class IDMTrainer(TrainerBase):
         b, c = ops.action_to_factored(jb.reshape(-1).to(torch.int64).contiguous(), jc.reshape(-1).to(torch.int64).contiguous(), n_camera_bins)
         return b.view(bsz, t, 20), c.view(bsz, t, 2)
 
-    def _checked_inputs(self, img_u8, buttons, camera, frame_weight):
+    def _checked_inputs(self, img_u8, buttons, camera, frame_weight, allow_zero_sum: bool = False):
         """Labels -> int64 [M, G] on the images' device, weights -> fp32 [M] (or None); the weights' sum and minimum and the labels' extrema come
         to the host in ONE transfer (one synchronisation per step).  ValueError on a label out of range, on a negative or non-finite weight and on
-        all-zero weights.  -> (buttons, camera, weights | None, weight sum)."""
+        all-zero weights (unless allow_zero_sum: a micro-batch of a window that carries weight elsewhere).  -> (buttons, camera, weights | None, weight sum)."""
         bsz, t = img_u8.shape[:2]
         m, dev = bsz * t, img_u8.device
         (gb, nb), (gc, nc) = self.engine.button_shape, self.engine.camera_shape
@@ -105,7 +105,7 @@ class IDMTrainer(TrainerBase):
         if w is not None:
             wsum = vals[4]
             self._check_weight_probe(wsum, vals[5])
-            if wsum == 0:
+            if wsum == 0 and not allow_zero_sum:
                 raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
         return ab, ac, w, wsum
 
@@ -183,25 +183,47 @@ class IDMTrainer(TrainerBase):
         return g
 
     @torch.no_grad()
-    def loss_and_grads(self, img_u8, buttons, camera, *, frame_weight=None, metrics: Optional[dict] = None, unscaled: bool = True):
+    def loss_and_grads(self, img_u8, buttons, camera, *, frame_weight=None, metrics: Optional[dict] = None, unscaled: bool = True,
+                       global_weight: Optional[float] = None, micro_batches: int = 1):
         """img_u8 uint8 [B, T, 128, 128, 3]; buttons int64 [B, T, 20] in {0, 1}; camera int64 [B, T, 2] in 0..10 -> (loss, grads of every trainable
         tensor).  frame_weight: [B, T] finite, non-negative (0 = a frame left out: exact zeros whatever it holds).  Labels out of range and bad
         weights raise ValueError before anything is queued (one host transfer).  metrics: a dict this call fills as BCTrainer.loss_and_grads does
         (loss, nll_* , entropy_*, acc_* = the fraction of groups whose arg-max is the label, weight_sum, frames, frame_nll, frame_out; device
-        tensors).  unscaled=False (what step() uses): in the fp16 mode the gradients stay multiplied by 1 / grad_unscale(sum w)."""
-        ab, ac, w, wsum = self._checked_inputs(img_u8, buttons, camera, frame_weight)
-        S = self.forward_saving(img_u8)
-        scale = (self.loss_scale if self.scaled else 1.0 / wsum) / self.engine.cfg["temperature"]
-        dz, frame_out, totals = ops.idm_loss(S["lp_b"], S["lp_c"], ab, ac, scale, weight=w, dtype=self.dtype)
-        loss = self._record_loss(frame_out, w, wsum)
+        tensors).  unscaled=False (what step() uses): in the fp16 mode the gradients stay multiplied by 1 / grad_unscale(sum w).
+        global_weight (default: this call's own frame count / weight sum): the count of a larger batch these frames are a part of -- the gradients
+        are this part's share of the gradient of THAT batch's mean loss (BCTrainer's global_frames), and all-zero weights are then legal.
+        micro_batches=K > 1 (gradient accumulation): the B sequences run as K row groups (micro_batch_rows) one after the other, each
+        carrying the whole call's count, their gradients summed in order (ops.grad_accumulate_); the loss and the metrics come from the groups'
+        totals summed in fp64, frame_nll / frame_out are the concatenations.  The inputs are checked once, for the whole batch."""
+        rows = self.micro_batch_rows(img_u8.shape[0], micro_batches) if micro_batches != 1 else None
+        ab, ac, w, wsum = self._checked_inputs(img_u8, buttons, camera, frame_weight, allow_zero_sum=global_weight is not None)
+        count = wsum if global_weight is None else float(global_weight)
+        self._weight_sum = count
+        bsz, t = img_u8.shape[:2]
+        if rows is None:
+            g, totals, frame_out = self._loss_and_grads_checked(img_u8, ab, ac, w, count)
+            loss = self._record_loss(frame_out, w, wsum)
+        else:
+            def run(k, lo, hi):
+                f = slice(lo * t, hi * t)
+                return self._loss_and_grads_checked(img_u8[lo:hi], ab[f], ac[f], None if w is None else w[f], count) + (None,)
+            g, totals, frame_out, _ = self._accumulated_window(rows, run)
+            loss = (totals[0] + totals[1]) / totals[6]
+        self._idm_totals = totals
         if metrics is not None:
-            self._fill_metrics(metrics, totals, frame_out, S["bsz"], S["t"])
+            self._fill_metrics(metrics, totals, frame_out, bsz, t)
             metrics["loss"] = loss
-        self._weight_sum = wsum
-        g = self.backward_from(S, dz)
         if unscaled and self.scaled:
-            self._unscale_(g, wsum)
+            self._unscale_(g, count)
         return loss, g
+
+    def _loss_and_grads_checked(self, img_u8, ab, ac, w, count: float):
+        """Forward, the fused loss and the backward of checked inputs (_checked_inputs) under the frame count `count` -> (grads -- in the fp16 mode
+        multiplied by 1 / grad_unscale(count) --, ops.idm_loss's totals [8], its records [M, 8])."""
+        S = self.forward_saving(img_u8)
+        scale = (self.loss_scale if self.scaled else 1.0 / count) / self.engine.cfg["temperature"]
+        dz, frame_out, totals = ops.idm_loss(S["lp_b"], S["lp_c"], ab, ac, scale, weight=w, dtype=self.dtype)
+        return self.backward_from(S, dz), totals, frame_out
 
     @torch.no_grad()
     def evaluate(self, img_u8, buttons, camera, *, frame_weight=None) -> dict:
@@ -218,11 +240,12 @@ class IDMTrainer(TrainerBase):
         return metrics
 
     @torch.no_grad()
-    def step(self, img_u8, buttons, camera, *, frame_weight=None, metrics: Optional[dict] = None) -> float:
+    def step(self, img_u8, buttons, camera, *, frame_weight=None, metrics: Optional[dict] = None, micro_batches: int = 1) -> float:
         """One Adam step (ops.adam_step_multi_: one launch for all tensors; in the fp16 mode it un-scales the gradients and leaves every tensor
         untouched when the overflow check fired; with max_grad_norm set the gradients are clipped by their global norm inside that launch and metrics gains
-        grad_norm / clip_coef / grad_norm_per_tensor -- TrainerBase._optimizer_tail).  Returns the loss.  The policy's next predict / label_video sees the new weights."""
+        grad_norm / clip_coef / grad_norm_per_tensor -- TrainerBase._optimizer_tail).  Returns the loss.  The policy's next predict / label_video sees the new weights.
+        micro_batches=K: loss_and_grads's gradient accumulation over K row groups; one Adam launch, clip and loss-scale decision for the window."""
         self._need_optimizer_state()
-        loss, grads = self.loss_and_grads(img_u8, buttons, camera, frame_weight=frame_weight, metrics=metrics, unscaled=False)
+        loss, grads = self.loss_and_grads(img_u8, buttons, camera, frame_weight=frame_weight, metrics=metrics, unscaled=False, micro_batches=micro_batches)
         loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._weight_sum), img_u8.device, metrics)
         return loss

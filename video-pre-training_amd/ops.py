@@ -868,6 +868,28 @@ def adam_step_multi_(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9, 
     return table   # (norm_out too outlives the enqueue: the Adam launch reads norm_out[1] on the device; a scratch one is freed in stream order)
 
 
+def grad_accumulate_(accs, grads):
+    """accs[i] += grads[i] for lists of contiguous fp32 tensors in ONE launch (vpt_grad_accumulate_multi): one fp32 add per element in the table
+    and block mapping of adam_step_multi_, no reductions, no atomics -- torch's `acc + g`, bit for bit.  inf / nan go through the sum.
+    ValueError on a length or size mismatch and when an accumulator shares storage with its addend.  Returns the table (keep it alive until the
+    launch has been enqueued; stream-ordered free afterwards)."""
+    accs, grads = list(accs), list(grads)
+    if len(accs) != len(grads):
+        raise ValueError(f"grad_accumulate_: {len(accs)} accumulators but {len(grads)} addends")
+    for i, (a, g) in enumerate(zip(accs, grads)):
+        if a.numel() != g.numel():
+            raise ValueError(f"grad_accumulate_: tensor {i} has {a.numel()} accumulator elements but {g.numel()} addend elements")
+        if a.dtype != torch.float32 or g.dtype != torch.float32 or not a.is_contiguous() or not g.is_contiguous():
+            raise ValueError(f"grad_accumulate_: tensor {i} must be contiguous fp32 on both sides")
+        if a.numel() and a.data_ptr() < g.data_ptr() + 4 * g.numel() and g.data_ptr() < a.data_ptr() + 4 * a.numel():
+            raise ValueError(f"grad_accumulate_: accumulator {i} shares storage with its addend (their elements overlap)")
+    if not accs:
+        return None
+    table, blk, numel = _adam_table(grads, accs, grads, grads)      # m, v: ignored by the kernel (any fp32 tensor of the size passes the table's checks)
+    _call("vpt_grad_accumulate_multi", dict(bytes=12.0 * numel), ptr(table), len(accs), blk, _stream())
+    return table
+
+
 def grads_nonfinite(grads):
     """int32 [1] device flag: 1 if any element of the fp32 tensors in `grads` is inf / nan (vpt_grads_nonfinite_multi, one launch; what
     torch.cuda.amp.GradScaler.unscale_ computes).  No host synchronisation here: the caller reads the flag when it needs it."""

@@ -74,8 +74,10 @@ class PPOTrainer(BCTrainer):
         return out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera), out["state_out"]
 
     # ------------------------------------------------------------------------------------------
-    def _frame_inputs(self, img_u8, act_buttons, act_camera, old_log_prob, advantage, value_target, prior_lp, frame_weight):
-        """Validation + flattening shared by loss_and_grads and evaluate -> dict of [M] device tensors, w / wsum, the priors."""
+    def _frame_inputs(self, img_u8, act_buttons, act_camera, old_log_prob, advantage, value_target, prior_lp, frame_weight, global_weight=None):
+        """Validation + flattening shared by loss_and_grads and evaluate -> dict of [M] device tensors, w / wsum, the priors.
+        global_weight: the weight sum of a larger batch these frames are a part of; it becomes `wsum` (the advantages' normalisation, when on, still
+        runs over THIS call's frames under this call's own sum), and all-zero weights of this call are then legal."""
         self._single_rank()
         if self.kl_coef > 0 and prior_lp is None:
             raise ValueError("PPOTrainer: kl_coef > 0 needs prior_lp = (lp_buttons, lp_camera) of the frozen prior (prior_logprobs)")
@@ -84,12 +86,14 @@ class PPOTrainer(BCTrainer):
         w, wsum = None, float(m)
         if frame_weight is not None:
             w, wsum = self._checked_weights(frame_weight, img_u8)
-            if wsum == 0:
+            if wsum == 0 and global_weight is None:
                 raise ValueError("frame_weight: every weight is zero (the loss sum w L / sum w is undefined)")
         f32 = lambda x, nme: self._per_frame(x, m, dev, nme)
         adv = f32(advantage, "advantage")
         if self.normalize_advantages:
             adv = self._normalized(adv, w, wsum)
+        if global_weight is not None:
+            wsum = float(global_weight)
         qb = qc = None
         if prior_lp is not None:
             qb, qc = (q.reshape(m, -1).to(torch.float32).contiguous() for q in prior_lp)
@@ -148,30 +152,59 @@ class PPOTrainer(BCTrainer):
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target, *, prior_lp=None,
-                       frame_weight=None, metrics: Optional[dict] = None, unscaled: bool = True):
+                       frame_weight=None, metrics: Optional[dict] = None, unscaled: bool = True, global_weight: Optional[float] = None,
+                       micro_batches: int = 1):
         """Forward (saving activations) + the fused loss + backward.  Returns (loss, grads dict incl. value_head.linear.*, state_out).
         act_*, old_log_prob, advantage, value_target: [B, T] -- the taken actions, act()'s `log_prob` at rollout time, advantages()'s two outputs.
         prior_lp: (lp_buttons, lp_camera) of the frozen prior on the same frames (prior_logprobs); required when kl_coef > 0, and with kl_coef = 0 it
         still fills the KL metrics.  frame_weight: [B, T] finite non-negative weights (0: padding, whatever the frame's inputs hold).
         metrics: a dict this call fills -- loss, pg_loss, kl_buttons, kl_camera, entropy_buttons, entropy_camera, value_loss (normalised space),
         clip_frac, approx_kl (mean of old_lp - lp), ratio_mean, weight_sum, frames, frame_out fp32 [B, T, 16] -- device tensors, nothing synchronises.
-        unscaled: as BCTrainer.loss_and_grads (False leaves the fp16 gradients multiplied by 1 / grad_unscale(self._global_frames), _loss_gradient_scale)."""
-        f = self._frame_inputs(img_u8, act_buttons, act_camera, old_log_prob, advantage, value_target, prior_lp, frame_weight)
-        S = self.forward_saving(img_u8, first, state_in)
+        unscaled: as BCTrainer.loss_and_grads (False leaves the fp16 gradients multiplied by 1 / grad_unscale(self._global_frames), _loss_gradient_scale).
+        global_weight (default: this call's own frame count / weight sum): the count of a larger batch these frames are a part of; _loss_gradient_scale
+        takes it, so the gradients are this part's share of the gradient of THAT batch's mean loss (all-zero weights are then legal).  Whoever cuts
+        a batch by hand normalises the advantages and updates the value normaliser over the whole batch first, with both switches of this trainer off.
+        micro_batches=K > 1 (gradient accumulation): the advantages' normalisation, the value normaliser's update and
+        _loss_gradient_scale run ONCE on the whole batch; then the B sequences run as K row groups (micro_batch_rows) one after the other under that
+        one (mean, std) pair and scale, their gradients summed in order (ops.grad_accumulate_).  The loss is _loss_of the groups' totals summed in
+        fp64; frame_out and state_out are the row-wise concatenations."""
+        rows = self.micro_batch_rows(img_u8.shape[0], micro_batches) if micro_batches != 1 else None
+        f = self._frame_inputs(img_u8, act_buttons, act_camera, old_log_prob, advantage, value_target, prior_lp, frame_weight, global_weight)
+        bsz, t = img_u8.shape[:2]
+        if rows is None:
+            S = self.forward_saving(img_u8, first, state_in)
+            vnorm = self._value_norm(f["target"], f["w"])
+            scale, self._global_frames = self._loss_gradient_scale(f["wsum"])
+            g, totals, frame_out, state_out = self._loss_and_backward(S, f, vnorm, scale)
+        else:
+            vnorm = self._value_norm(f["target"], f["w"])
+            scale, self._global_frames = self._loss_gradient_scale(f["wsum"])
+            first = torch.as_tensor(first)
+
+            def run(k, lo, hi):
+                fk = {q: (x[lo * t:hi * t] if isinstance(x, torch.Tensor) else x) for q, x in f.items()}
+                S = self.forward_saving(img_u8[lo:hi], first[lo:hi], self._tree_rows(state_in, lo, hi))
+                return self._loss_and_backward(S, fk, vnorm, scale)
+
+            g, totals, frame_out, states = self._accumulated_window(rows, run)
+            state_out = self._tree_cat_rows(states)
+        self._rl_totals = totals
+        loss = self._loss_of(totals)
+        if metrics is not None:
+            self._fill_rl_metrics(metrics, totals, frame_out, bsz, t)
+        if unscaled and self.scaled:
+            self._unscale_(g, self._global_frames)
+        return loss, g, state_out
+
+    def _loss_and_backward(self, S, f, vnorm, scale):
+        """ops.rl_loss on a saving forward's log-probs and the backward behind it -> (grads, totals [16], records [M, 16], state_out).
+        f: _frame_inputs's dict (or its rows); vnorm, scale: _value_norm's pair and _loss_gradient_scale's factor."""
         nb, nc = self.engine.n_buttons, self.engine.n_camera
-        vnorm = self._value_norm(f["target"], f["w"])
-        scale, self._global_frames = self._loss_gradient_scale(f["wsum"])
         dz, frame_out, totals = ops.rl_loss(S["lp_b"], S["lp_c"], f["ab"], f["ac"], f["old"], f["adv"], S["ldz"], scale, prior_buttons=f["qb"],
                                             prior_camera=f["qc"], value=S["logits"][:, nb + nc], value_target=f["target"], vnorm=vnorm, weight=f["w"],
                                             clip=self.clip, kl_coef=self.kl_coef, entropy_coef=self.entropy_coef, value_coef=self.value_coef,
                                             temperature=self.engine.cfg["temperature"], dtype=self.dtype)
-        loss = self._loss_of(totals)
-        if metrics is not None:
-            self._fill_rl_metrics(metrics, totals, frame_out, S["bsz"], S["t"])
-        g = self.backward_from(S, dz, value_grads=True)
-        if unscaled and self.scaled:
-            self._unscale_(g, self._global_frames)
-        return loss, g, S["state_out"]
+        return self.backward_from(S, dz, value_grads=True), totals, frame_out, S["state_out"]
 
     @torch.no_grad()
     def evaluate(self, img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target, *, prior_lp=None, frame_weight=None):
@@ -195,11 +228,13 @@ class PPOTrainer(BCTrainer):
 
     @torch.no_grad()
     def step(self, img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target, *, prior_lp=None, frame_weight=None,
-             metrics: Optional[dict] = None):
-        """One optimiser step on a [B, T] chunk.  Returns (loss, state_out).  The Adam launch, the optional gradient-norm clip and the loss-scale
+             metrics: Optional[dict] = None, micro_batches: int = 1):
+        """One optimiser step on a [B, T] chunk.  Returns (loss, state_out).  micro_batches=K: loss_and_grads's gradient accumulation over K row
+        groups; one Adam launch, clip and loss-scale decision for the window.  The Adam launch, the optional gradient-norm clip and the loss-scale
         bookkeeping are BCTrainer.step's (TrainerBase._optimizer_tail; metrics gains grad_norm / clip_coef / grad_norm_per_tensor when max_grad_norm is set)."""
         self._need_optimizer_state()
         loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target,
-                                                     prior_lp=prior_lp, frame_weight=frame_weight, metrics=metrics, unscaled=False)
+                                                     prior_lp=prior_lp, frame_weight=frame_weight, metrics=metrics, unscaled=False,
+                                                     micro_batches=micro_batches)
         loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._global_frames), img_u8.device, metrics)
         return loss, state_out

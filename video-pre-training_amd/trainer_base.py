@@ -170,6 +170,68 @@ class TrainerBase(CnnTrainingMixin):
         if frame_out is not None:
             metrics.update(frame_nll=(frame_out[:, 0] + frame_out[:, 1]).view(bsz, t), frame_out=frame_out.view(bsz, t, 8))
 
+    # ---- gradient accumulation over micro-batches: a micro-batch is a data-parallel rank that runs later on the same card --------
+    @staticmethod
+    def micro_batch_rows(bsz: int, micro_batches: int) -> List[tuple]:
+        """The [begin, end) row groups the batch's `bsz` sequences are cut into: distributed.shard_range, the cut of the data-parallel step.
+        ValueError unless 1 <= micro_batches <= bsz (every group holds at least one sequence)."""
+        from .distributed import shard_range
+        k = int(micro_batches)
+        if k != micro_batches or k < 1 or k > int(bsz):
+            raise ValueError(f"micro_batches must be an integer in 1..{int(bsz)} (the batch's sequences), got {micro_batches!r}")
+        return [shard_range(int(bsz), i, k) for i in range(k)]
+
+    @staticmethod
+    def sum_totals(totals: List[torch.Tensor]) -> torch.Tensor:
+        """The micro-batches' totals vectors (8 of ops.bc_loss / ops.idm_loss, 16 of ops.rl_loss) summed in fp64 IN ORDER, then rounded to fp32 --
+        what the data-parallel step's final reduction does with the ranks' totals."""
+        acc = totals[0].to(torch.float64)
+        for t_ in totals[1:]:
+            acc = acc + t_.to(torch.float64)
+        return acc.to(torch.float32)
+
+    @staticmethod
+    def _tree_rows(tree, lo: int, hi: int):
+        """Rows [lo, hi) of every tensor in a nest of tuples / lists (the recurrent state: [B, ...] leaves, None passes through)."""
+        if tree is None:
+            return None
+        if isinstance(tree, torch.Tensor):
+            return tree[lo:hi]
+        return type(tree)(TrainerBase._tree_rows(x, lo, hi) for x in tree)
+
+    @staticmethod
+    def _tree_cat_rows(trees: list):
+        """The inverse: the row-wise concatenation of nests of one structure, in order."""
+        head = trees[0]
+        if head is None:
+            return None
+        if isinstance(head, torch.Tensor):
+            return torch.cat(trees, 0)
+        return type(head)(TrainerBase._tree_cat_rows([tr[i] for tr in trees]) for i in range(len(head)))
+
+    def _accumulate_grads(self, acc: Optional[Dict[str, torch.Tensor]], g: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """acc None: the first micro-batch's gradient tensors become the accumulators as they are (no arithmetic).  Otherwise acc[n] += g[n] for
+        every trainable tensor in ONE ops.grad_accumulate_ launch."""
+        names = [n for n in self.trainable if n in g]
+        if acc is None:
+            return {n: g[n].contiguous() for n in names}
+        ops.grad_accumulate_([acc[n].view(-1) for n in names], [g[n].contiguous().view(-1) for n in names])
+        return acc
+
+    def _accumulated_window(self, rows: List[tuple], run_micro_batch, accumulate=None):
+        """The loop every trainer's micro_batches=K shares.  run_micro_batch(k, lo, hi) -> (grads of rows [lo, hi) carrying the WINDOW's frame
+        count, its totals vector, its frame records, anything else the trainer wants back), one micro-batch at a time: its gradient dict is
+        folded into the accumulators and released -- with its activations, which run_micro_batch let go -- before the next forward starts.
+        accumulate(k, acc, g) -> acc replaces _accumulate_grads (the data-parallel step accumulates in its arenas).
+        -> (accumulated grads, totals summed by sum_totals, records concatenated to [M, .], the list of the extras)."""
+        acc, totals, records, extras = None, [], [], []
+        for k, (lo, hi) in enumerate(rows):
+            g, tot, rec, extra = run_micro_batch(k, lo, hi)
+            acc = self._accumulate_grads(acc, g) if accumulate is None else accumulate(k, acc, g)
+            del g
+            totals.append(tot); records.append(rec); extras.append(extra)
+        return acc, self.sum_totals(totals), torch.cat(records, 0), extras
+
     # ---- the optimiser tail of every trainer's step(): the Adam launch, gradient-norm clipping and the loss-scale bookkeeping --------------
     def _optimizer_tail(self, loss, grads, grad_scale: float, device, metrics=None):
         """The Adam launch for every trainable tensor of `grads` + the bookkeeping -> (float(loss), skipped).

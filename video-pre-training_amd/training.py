@@ -289,8 +289,14 @@ class BCTrainer(TrainerBase):
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def reduced_loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None):
+    def reduced_loss_and_grads(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None,
+                               micro_batches: int = 1):
         """This rank's shard of the batch -> (global mean loss, gradients of the GLOBAL mean loss summed over ranks, state_out).
+        micro_batches=K > 1 (gradient accumulation): the shard's B sequences run as K contiguous row groups (micro_batch_rows) one
+        after the other, each carrying the window's frame count, their gradients summed in order (the first adopted, then one ops.grad_accumulate_
+        launch each) -- a micro-batch's activations are gone before the next forward, so the peak is that of B / K sequences.  Loss and metrics come
+        from the micro-batches' totals summed in fp64 (the arithmetic of the data-parallel fused path; the loss path is always ops.bc_loss);
+        frame_nll / frame_out / state_out are the row-wise concatenations.  Across ranks: ONE count reduction and ONE exchange per window.
         frame_weight / metrics: as loss_and_grads.  With weights the count the ranks agree on is sum_ranks sum w (fp64), the loss is
         sum_ranks(sum w nll) / that, and a rank whose shard carries no weight is legal while the global sum is positive; requested metrics
         are GLOBAL (the eight totals travel in the final reduction, next to the health flag); frame_nll / frame_out are this rank's frames.
@@ -304,12 +310,21 @@ class BCTrainer(TrainerBase):
         # (self.exchange = False: the local step only -- bench.py times it beside the full step to report how much of the exchange the CNN backward hides)
         world = dist.get_world_size() if dist.is_initialized() and getattr(self, "exchange", True) else 1
         m_local = img_u8.shape[0] * img_u8.shape[1]
+        rows = self.micro_batch_rows(img_u8.shape[0], micro_batches) if micro_batches != 1 else None      # (ValueError before anything is queued)
         self._global_frames = m_local
         # force_exchange (VPT_DP_FORCE_EXCHANGE=1): take the data-parallel path in a ONE-rank group too -- the frame-count reduction, both arenas, the early exchange
         # under the CNN backward, the late one, the health reduction -- so that the whole step can be run (and timed) over the real transport on a 1-GPU box
         force = bool(getattr(self, "force_exchange", False)) and dist.is_initialized()
-        fused = frame_weight is not None or metrics is not None      # the loss path through ops.bc_loss (its totals), else the unchanged default
+        fused = frame_weight is not None or metrics is not None or rows is not None      # the loss path through ops.bc_loss (its totals), else the unchanged default
         if world == 1 and not force:
+            if rows is not None:
+                w, wsum = self._checked_weights(frame_weight, img_u8) if frame_weight is not None else (None, None)
+                if wsum is not None:
+                    if wsum == 0:
+                        raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
+                    self._global_frames = wsum
+                grads, totals, state_out = self._micro_batched(rows, img_u8, first, state_in, act_buttons, act_camera, w, self._global_frames, metrics)
+                return (totals[0] + totals[1]) / totals[6], grads, state_out
             if not fused:
                 return self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=m_local, unscaled=False)
             w, wsum = self._checked_weights(frame_weight, img_u8) if frame_weight is not None else (None, None)
@@ -339,7 +354,7 @@ class BCTrainer(TrainerBase):
                 err = ValueError("frame_weight: every weight of the global batch is zero (the loss sum w nll / sum w is undefined)")
         early = [n for n in self.trainable if not n.startswith("net.img_process.cnn.")]   # final before the CNN backward
         late = [n for n in self.trainable if n.startswith("net.img_process.cnn.")]
-        pending, state = [], dict(early_sent=False)
+        pending, state = [], dict(early_sent=False, accumulated=False)
         # the gradients live in two flat fp32 arenas that persist across steps (distributed.GradArena): each tensor is copied in once when it
         # is final, the collectives run in place on 64 MB slices of the arena, the optimiser reads the views -- no cat, no copy back
         akey = (tuple(early), tuple(late), tuple(tuple(self.params[n].shape) for n in early + late), str(dev))
@@ -348,23 +363,37 @@ class BCTrainer(TrainerBase):
         arena_early, arena_late = self._arenas[1]
 
         def start_trunk_exchange(g):
-            arena_early.adopt(g)
+            if state["accumulated"]:      # the window's earlier micro-batches are in the arena: add this one's trunk + head gradients to them
+                arena_early.accumulate(g)
+            else:
+                arena_early.adopt(g)
             pending.extend(arena_early.all_reduce_start(force))
             state["early_sent"] = True
+
+        def into_arenas(k, acc, g):       # micro-batches 0 .. K-2 whole, and the last one's CNN gradients: straight into the two arenas
+            last = k == len(rows) - 1
+            for arena in ((arena_late,) if last else (arena_early, arena_late)):
+                (arena.accumulate if state["accumulated"] else arena.adopt)(g)
+            state["accumulated"] = True
+            return g if last else {n: g[n] for n in early + late}      # (the arenas' views)
 
         loss, grads, state_out = None, None, None
         local_metrics = {} if metrics is not None else None
         try:
             if err is not None:
                 raise err
-            if fused:
+            if rows is not None:
+                grads, self._bc_totals, state_out = self._micro_batched(rows, img_u8, first, state_in, act_buttons, act_camera, w, m_global, local_metrics,
+                                                                        accumulate=into_arenas, on_last_trunk_grads=start_trunk_exchange)
+            elif fused:
                 loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, global_frames=m_global,
                                                              on_trunk_grads=start_trunk_exchange, unscaled=False, frame_weight=w,
                                                              metrics=local_metrics, _weight_sum=wsum)
             else:
                 loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera,
                                                              global_frames=m_global, on_trunk_grads=start_trunk_exchange, unscaled=False)
-            arena_late.adopt(grads)
+            if rows is None:
+                arena_late.adopt(grads)
             pending.extend(arena_late.all_reduce_start(force))
         except Exception as e:          # e.g. out of memory on this rank: still take part in every collective (with zeros of
             err = e                     # the same shapes) so that the other ranks are not left blocked, then fail everywhere
@@ -393,12 +422,40 @@ class BCTrainer(TrainerBase):
             raise RuntimeError(f"BC step failed on {'this' if err is not None else 'another'} rank: {err!r}")
         return tail[0] / m_global, grads, state_out
 
+    def _micro_batched(self, rows, img_u8, first, state_in, act_buttons, act_camera, w, count, metrics, accumulate=None, on_last_trunk_grads=None):
+        """The K > 1 window of reduced_loss_and_grads on this rank: loss_and_grads per row group with global_frames = `count` (the window's frame
+        count or weight sum, all ranks'), w: the checked fp32 [M] weights or None -> (accumulated grads, the summed totals [8], state_out of all rows).
+        `metrics` (when a dict) is filled from the summed totals and the concatenated records.  on_last_trunk_grads: loss_and_grads's callback, for the
+        LAST micro-batch only (the data-parallel step starts its early exchange there); accumulate: TrainerBase._accumulated_window's."""
+        bsz, t = img_u8.shape[:2]
+        first = torch.as_tensor(first)
+        ab, ac = act_buttons.reshape(bsz, t), act_camera.reshape(bsz, t)
+        w_rows = w.view(bsz, t) if w is not None else None
+
+        def run(k, lo, hi):
+            local: dict = {}
+            # (_weight_sum: the rows' own sum would only feed this micro-batch's own loss, which the window does not read -- no host transfer)
+            _, g, s_out = self.loss_and_grads(img_u8[lo:hi], first[lo:hi], self._tree_rows(state_in, lo, hi), ab[lo:hi], ac[lo:hi], global_frames=count,
+                                              on_trunk_grads=on_last_trunk_grads if k == len(rows) - 1 else None, unscaled=False,
+                                              frame_weight=None if w_rows is None else w_rows[lo:hi].reshape(-1), metrics=local,
+                                              _weight_sum=None if w_rows is None else count)
+            return g, self._bc_totals, local["frame_out"].reshape(-1, 8), s_out
+
+        grads, totals, records, states = self._accumulated_window(rows, run, accumulate)
+        if metrics is not None:
+            self._fill_metrics(metrics, totals, records, bsz, t)
+        return grads, totals, self._tree_cat_rows(states)
+
     @torch.no_grad()
-    def step(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None):
+    def step(self, img_u8, first, state_in, act_buttons, act_camera, *, frame_weight=None, metrics: Optional[dict] = None, micro_batches: int = 1):
         """One optimiser step on this rank's shard of the batch.  Returns (global mean loss, state_out).  frame_weight / metrics: as
-        loss_and_grads (the weighted loss sum w nll / sum w over all ranks; global metrics)."""
+        loss_and_grads (the weighted loss sum w nll / sum w over all ranks; global metrics).  micro_batches=K: the shard runs as K row groups
+        whose gradients are accumulated (reduced_loss_and_grads); ONE Adam launch, clip and loss-scale decision per window."""
         self._need_optimizer_state()
-        if frame_weight is None and metrics is None:
+        if micro_batches != 1:
+            loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, frame_weight=frame_weight, metrics=metrics,
+                                                                 micro_batches=micro_batches)
+        elif frame_weight is None and metrics is None:
             loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera)
         else:
             loss, grads, state_out = self.reduced_loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, frame_weight=frame_weight, metrics=metrics)
