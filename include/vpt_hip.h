@@ -84,10 +84,12 @@ int vpt_chw_to_blocked(const float* src, float* dst, int64_t rows, int C, int H,
  *   VPT_WS_FULL_ATTENTION_BACKWARD (B, t, hid, -, -)         vpt_full_attention_backward's dkv_slab (one slot per 32-query tile)
  *   VPT_WS_CONV3D_T5_BACKWARD    (frames, H, W, -, Cout)     vpt_conv3d_t5_backward's partials (one slab row per workgroup + the reduction's scratch)
  *   VPT_WS_RL_LOSS               (M, -, -, -, -)             vpt_rl_loss's workspace (the [M][16] record slab + its reduction scratch)
+ *   VPT_WS_PPG_AUX_LOSS          (M, -, -, -, -)             vpt_ppg_aux_loss's workspace (the [M][8] record slab + its reduction scratch)
  * Returns -1 for an unknown op. */
 enum { VPT_WS_CONV3X3_WGRAD = 1, VPT_WS_CONV_BACKWARD_PREPARE = 2, VPT_WS_LINEAR_SPLITK = 3, VPT_WS_LAYERNORM_BACKWARD = 4, VPT_WS_COLUMN_SUM = 5,
        VPT_WS_ATTENTION_BACKWARD_DKV = 6, VPT_WS_ATTENTION_BACKWARD_DBND = 7, VPT_WS_FRAME_AFFINE_BACKWARD = 8, VPT_WS_CONV_FIRST_BACKWARD = 9,
-       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11, VPT_WS_CONV3D_T5_BACKWARD = 12, VPT_WS_RL_LOSS = 13 };
+       VPT_WS_BC_LOSS = 10, VPT_WS_FULL_ATTENTION_BACKWARD = 11, VPT_WS_CONV3D_T5_BACKWARD = 12, VPT_WS_RL_LOSS = 13,
+       VPT_WS_PPG_AUX_LOSS = 14 };
 int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout);
 int vpt_pack_conv3x3(const float* weight, const float* gain, const float* bias, void* wpk, float* edge_sa, float* edge_sg,
                      int Cout, int Cin, void* stream);
@@ -505,6 +507,32 @@ int vpt_rl_loss(const float* lp_buttons, const float* lp_camera, const float* pr
                 const float* value, int64_t value_stride, const float* value_target, const float* vnorm, const float* weight,
                 void* dz, float* frame_out, float* totals, float* workspace, int M, int nb, int nc, int ldz,
                 float clip, float kl_coef, float entropy_coef, float value_coef, float temperature, float scale, void* stream);
+
+/* The auxiliary ("sleep") phase of phasic policy gradient for one network with one value head: a cloning term that holds the policy at a snapshot
+ * pi_old + the value loss, their gradient w.r.t. the fused head logits and their metrics in ONE sweep over the log-probs.  With l, m the log-probs of
+ * the policy and of the snapshot, p = expf(l), o = expf(m), per head
+ *   D = sum o (m - l)  (a term with o = 0 counts 0),   S = sum o  (the teacher's mass, a diagnostic),   t^ = (value_target - mean) / std,
+ *   L_r = clone_coef (D_b + D_c) + value_coef (v - t^)^2,   loss = sum_rows w L / sum_rows w.
+ * The KL is KL(pi_old || pi): the expectation runs over the STORED TEACHER -- the opposite direction of vpt_rl_loss's KL(pi || prior), whose
+ * expectation runs over the current policy.  It is the cross-entropy to a soft label minus the label's own entropy; with a one-hot teacher (m = 0 at
+ * the label, -inf elsewhere) D is vpt_bc_loss's NLL and the policy columns of dz are that kernel's, bit for bit.
+ * The gradient convention: dz holds p - o, the gradient of D for a teacher whose mass is EXACTLY 1.  The exact gradient is p S - o; frame_out carries
+ * S_b and S_c so that a caller sees how far a teacher is from 1 (a snapshot stored in fp32: a few 1e-7 per class).
+ * value, value_target, vnorm and weight are vpt_rl_loss's (value may be NULL: no value term, value_target and vnorm are then not read); old_buttons and
+ * old_camera are both required.  A coefficient of 0 skips its term.  A class with o > 0 and l = -inf (live at the snapshot, masked now) gives
+ * D = +inf with a finite dz: take the snapshot under the same logit masks.  Every output is optional (NULL):
+ *   dz        16-bit [M][ldz], ldz >= nb + nc + 1:  (clone_coef (p - o)) rst per head, rst = (scale weight[row]) / temperature;
+ *             column nb + nc: ((2 value_coef) (v - t^)) (scale weight[row]); further columns zero.  The caller folds 1 / sum w (and the fp16 loss scale)
+ *             into `scale`.
+ *   frame_out fp32 [M][8]: D_b, D_c, (v - t^)^2, S_b, S_c, w, 1 if w > 0, 0 -- the frame's own, unweighted values;
+ *   totals    fp32 [8]: sum_rows w frame_out[row][k] for k < 5, sum w, the number of rows with w > 0, 0; added in a fixed order through `workspace`
+ *             (vpt_workspace_bytes(VPT_WS_PPG_AUX_LOSS, M, ...) bytes, required with totals; M <= 65536, -2 above it): no atomics, the same inputs
+ *             give the same bits.
+ * A row with weight 0 stores exact zeros in dz and adds exact zeros to totals whatever its inputs hold (NaN included). */
+int vpt_ppg_aux_loss(const float* lp_buttons, const float* lp_camera, const float* old_buttons, const float* old_camera,
+                     const float* value, int64_t value_stride, const float* value_target, const float* vnorm, const float* weight,
+                     void* dz, float* frame_out, float* totals, float* workspace, int M, int nb, int nc, int ldz,
+                     float clone_coef, float value_coef, float temperature, float scale, void* stream);
 
 /* Generalised advantage estimation over [B][T] rollouts (reward, value fp32; first uint8: frame t starts an episode; last_value [B] and next_first [B]
  * describe the frame after the rollout; `value` and `ret` are denormalised, lib/scaled_mse_head.py:45-47):

@@ -1,16 +1,20 @@
-"""Time the PPO fine-tuning step against the same loss written in torch on the autograd boundary and against the BC step, interleaved in ONE process.
+"""Time the PPO fine-tuning step and the PPG auxiliary step against the same losses written in torch on the autograd boundary and against the BC step,
+interleaved in ONE process.
 python tools/rl_bench.py [--model 2x] [--batch 64] [--seq 128] [--warmup 1] [--steps 2] [--no-cnn] [--parent-tree DIR]
 
   ppo        PPOTrainer.step with kl_coef > 0 (the prior's log-probs precomputed): ONE vpt_rl_loss launch between forward and backward
   torch      the same loss written in torch on get_output_for_observation's outputs, .backward() through the autograd boundary, torch.optim.Adam
+  aux        PPOTrainer.aux_step (the PPG auxiliary phase; the snapshot precomputed, outside the timing): ONE vpt_ppg_aux_loss launch
+  aux_torch  the auxiliary loss written in torch on the same boundary, the same torch.optim.Adam
   bc         BCTrainer.step of this tree
   bc_parent  BCTrainer.step of another checkout of the project (--parent-tree: its package directory with its own built libraries), loaded beside
              this one under another module name -- the parent commit's step, on the same box at the same clock
+  ppo_parent PPOTrainer.step of that checkout
 
 Every timed step sits between two HIP events; the variants take turns inside every round (warm-up and round counts as tools/bc_bench.py: 1 and 2 by
 default), each turn one un-timed step (the caching allocator re-shapes its pools after a switch of variant: seconds, measured) and the timed one; the
-spread of a variant is max - min over its rounds.  Then one instrumented PPO step and one weighted BC step give the two loss kernels' own
-times.  The last line is one JSON record."""
+spread of a variant is max - min over its rounds.  Then one instrumented PPO step, one auxiliary step and one weighted BC step give the three loss
+kernels' own times.  The last line is one JSON record."""
 import argparse, importlib.util, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -61,6 +65,8 @@ prior = (qb.clone(), qc.clone())
 old = (prior[0].gather(1, ab.reshape(M, 1)) + prior[1].gather(1, ac.reshape(M, 1))).reshape(B, T) + 0.1 * torch.randn(B, T, generator=g).to(dev)
 del qb, qc
 variants["ppo"] = lambda: tr_ppo.step(img, first, pol_ppo.initial_state(B), ab, ac, old, adv, target, prior_lp=prior)[0]
+# the auxiliary phase runs on the SAME trainer (one network, one optimiser); its snapshot is the log-probs taken above, before any step
+variants["aux"] = lambda: tr_ppo.aux_step(img, first, pol_ppo.initial_state(B), prior, target)[0]
 
 # ---- (ii) the same loss in torch on the autograd boundary + torch.optim.Adam ---------------------------------------------------
 if "torch" not in skip:
@@ -86,6 +92,18 @@ if "torch" not in skip:
         return float(loss.detach())
     variants["torch"] = torch_step
 
+    def torch_aux_step():
+        (pd, vpred, _), _ = pol_t({"img": img}, first, pol_t.initial_state(B))
+        lb, lc = pd["buttons"].reshape(M, NB), pd["camera"].reshape(M, NC)
+        kl = (prior[0].exp() * (prior[0] - lb)).sum(-1) + (prior[1].exp() * (prior[1] - lc)).sum(-1)
+        that = pol_t.value_head.normalizer.normalize(target.reshape(M, 1)).reshape(M)
+        loss = (tr_ppo.clone_coef * kl + tr_ppo.aux_value_coef * (vpred.reshape(M) - that) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        return float(loss.detach())
+    variants["aux_torch"] = torch_aux_step
+
 # ---- (iii) BCTrainer.step, this tree and the parent's ---------------------------------------------------------------------------
 pol_bc = make_policy()
 tr_bc = BCTrainer(pol_bc, train_cnn=not a.no_cnn)
@@ -105,6 +123,10 @@ if a.parent_tree:
     pol_par = make_policy(ParentPolicy, pconfigs, parent_space)
     tr_par = ParentBCTrainer(pol_par, train_cnn=not a.no_cnn)
     variants["bc_parent"] = lambda: tr_par.step(img, first, pol_par.initial_state(B), ab, ac)[0]
+    from vpt_amd_parent.rl_training import PPOTrainer as ParentPPOTrainer
+    pol_ppar = make_policy(ParentPolicy, pconfigs, parent_space)
+    tr_ppar = ParentPPOTrainer(pol_ppar, train_cnn=not a.no_cnn, normalize_advantages=False, **COEF)
+    variants["ppo_parent"] = lambda: tr_ppar.step(img, first, pol_ppar.initial_state(B), ab, ac, old, adv, target, prior_lp=prior)[0]
 variants = {k: v for k, v in variants.items() if k not in skip}
 
 # ---- interleaved timing -----------------------------------------------------------------------------------------------------------
@@ -130,15 +152,16 @@ for k, v in times.items():
     rec[k] = dict(ms_median=round(sorted(v)[len(v) // 2], 2), ms_mean=round(sum(v) / len(v), 2), ms_min=round(min(v), 2), ms_max=round(max(v), 2), spread_ms=round(max(v) - min(v), 2))
     print(f"{k:10s} step {rec[k]['ms_mean']:9.2f} ms  (min {min(v):.2f}, max {max(v):.2f}; {M / (rec[k]['ms_mean'] * 1e-3):.0f} frames/s)")
 
-# ---- the two loss kernels' own times ----------------------------------------------------------------------------------------------
+# ---- the three loss kernels' own times --------------------------------------------------------------------------------------------
 ops.TIMER.enabled = True
-for name, fn, key in (("ppo", variants["ppo"], "vpt_rl_loss"),
+for name, fn, key in (("ppo", variants["ppo"], "vpt_rl_loss"), ("aux", variants["aux"], "vpt_ppg_aux_loss"),
                       ("bc", lambda: tr_bc.step(img, first, pol_bc.initial_state(B), ab, ac, frame_weight=torch.ones(B, T, device=dev), metrics={}), "vpt_bc_loss")):
     ops.TIMER.reset()
     fn()
     torch.cuda.synchronize()
     summ = ops.TIMER.summary()
     rec[key + "_ms"] = round(summ[key]["ms"], 4)
+    rec[key + "_bytes"] = summ[key]["bytes"]
     rec[name + "_kernel_total_ms"] = round(sum(v["ms"] for v in summ.values()), 2)
     print(f"{key}: {summ[key]['ms']:.4f} ms of {rec[name + '_kernel_total_ms']:.1f} ms kernel time in an instrumented {name} step "
           f"({summ[key]['bytes'] / (summ[key]['ms'] * 1e-3) / 1e12:.2f} TB/s over its own bytes)")

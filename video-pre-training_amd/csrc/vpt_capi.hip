@@ -83,6 +83,7 @@ int64_t vpt_workspace_bytes(int op, int frames, int H, int W, int Cin, int Cout)
     case VPT_WS_FULL_ATTENTION_BACKWARD: return 4 * (int64_t)vpt_full_attn_bwd_dkv_floats(frames, H, W);    /* (B, t, hid) */
     case VPT_WS_CONV3D_T5_BACKWARD: return 4 * (int64_t)vpt_conv3d_bwd_partial_floats(frames, H, W, Cout);
     case VPT_WS_RL_LOSS: return 4 * (int64_t)vpt_rl_loss_workspace_floats(frames);                          /* (M) */
+    case VPT_WS_PPG_AUX_LOSS: return 4 * (int64_t)vpt_ppg_aux_loss_workspace_floats(frames);                /* (M) */
     case VPT_WS_LINEAR_SPLITK: return 4 * (int64_t)frames * H * (int64_t)W;   /* splitk (= frames) x M (= H) x N (= W) fp32 partial slices */
     default: return -1;
   }
@@ -632,6 +633,27 @@ int vpt_rl_loss(const float* lp_buttons, const float* lp_camera, const float* pr
   a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz;
   a.clip = clip; a.kl_coef = kl_coef; a.entropy_coef = entropy_coef; a.value_coef = value_coef; a.inv_temp = 1.0f / temperature; a.scale = scale;
   CHECK_LAUNCH(vpt_rl_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_rl_loss");
+}
+
+int vpt_ppg_aux_loss(const float* lp_buttons, const float* lp_camera, const float* old_buttons, const float* old_camera,
+                     const float* value, int64_t value_stride, const float* value_target, const float* vnorm, const float* weight,
+                     void* dz, float* frame_out, float* totals, float* workspace, int M, int nb, int nc, int ldz,
+                     float clone_coef, float value_coef, float temperature, float scale, void* stream) {
+  if (!lp_buttons || !lp_camera) return fail(-1, "vpt_ppg_aux_loss: null log-probs");
+  if (!old_buttons || !old_camera) return fail(-1, "vpt_ppg_aux_loss: null snapshot log-probs (both heads are required)");
+  if (M <= 0 || nb <= 0 || nc <= 0) return fail(-1, "vpt_ppg_aux_loss: M and the head widths must be positive");
+  if (value && (!value_target || !vnorm)) return fail(-1, "vpt_ppg_aux_loss: the value term needs value_target and vnorm");
+  if (value && value_stride < 1) return fail(-1, "vpt_ppg_aux_loss: value_stride must be positive");
+  if (dz && ldz < nb + nc + 1) return fail(-1, "vpt_ppg_aux_loss: ldz < nb + nc + 1");
+  if (!(temperature > 0.f)) return fail(-1, "vpt_ppg_aux_loss: temperature must be positive");
+  if (totals && !workspace) return fail(-1, "vpt_ppg_aux_loss: totals need the workspace (VPT_WS_PPG_AUX_LOSS)");
+  if (totals && M > 65536) return fail(-2, "vpt_ppg_aux_loss: totals of at most 65536 rows");
+  VptPpgAuxLossArgs a = {};
+  a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.old_buttons = old_buttons; a.old_camera = old_camera;
+  a.value = value; a.value_stride = (long)value_stride; a.value_target = value_target; a.vnorm = vnorm; a.weight = weight;
+  a.dz = (vpt_op16*)dz; a.frame_out = frame_out; a.M = M; a.nb = nb; a.nc = nc; a.ldz = ldz;
+  a.clone_coef = clone_coef; a.value_coef = value_coef; a.inv_temp = 1.0f / temperature; a.scale = scale;
+  CHECK_LAUNCH(vpt_ppg_aux_loss_launch(&a, totals, workspace, (hipStream_t)stream), "vpt_ppg_aux_loss");
 }
 
 int vpt_gae(const float* reward, const float* value, const uint8_t* first, const float* last_value, const uint8_t* next_first,

@@ -358,6 +358,23 @@ struct VptRlLossArgs {      // clipped policy gradient + KL(pi || prior) + entro
   float clip, kl_coef, entropy_coef, value_coef, inv_temp, scale;
 };
 
+struct VptPpgAuxLossArgs {  // PPG auxiliary phase: clone_coef KL(pi_old || pi) + value_coef (v - t^)^2 of a frame in one sweep (vpt_ppg_aux_loss_kernel, vpt_ppg.hip)
+  const float* lp_buttons; // [M][nb] the current policy's log-probabilities (forward output)
+  const float* lp_camera;  // [M][nc]
+  const float* old_buttons;     // [M][nb] / [M][nc] log-probabilities of the snapshot pi_old (the teacher; both required)
+  const float* old_camera;
+  const float* value;      // optional: the raw value output (normalised space) of frame r at value[r * value_stride]; null: no value term
+  const float* value_target;    // [M] denormalised returns (read only with `value`)
+  const float* vnorm;      // device [2]: the value normaliser's (mean, std) (read only with `value`)
+  const float* weight;     // optional [M] per-frame weights (null: all ones); a row with weight 0 writes exact zeros to dz and to its slab record
+  vpt_op16* dz;            // optional [M][ldz], ldz >= nb + nc + 1: (clone_coef (p - o)) (scale w inv_temp), the value column, further columns zero
+  float* frame_out;        // optional [M][8]: D_b, D_c, (v - t^)^2, S_b, S_c, w, w > 0, 0 (unweighted)
+  float* slab;             // set by the launcher: [M][8] weighted records, summed by vpt_slab_sum into the totals
+  long value_stride;
+  int M, nb, nc, ldz;
+  float clone_coef, value_coef, inv_temp, scale;
+};
+
 struct VptGaeArgs {         // generalised advantage estimation, one lane per sequence (vpt_gae_kernel)
   const float* reward;     // [B][T]
   const float* value;      // [B][T] denormalised value predictions
@@ -504,6 +521,8 @@ int vpt_bc_loss_launch(const VptBcLossArgs* a, float* totals, float* workspace, 
 int vpt_idm_loss_launch(const VptIdmLossArgs* a, float* totals, float* workspace, hipStream_t s);
 long vpt_rl_loss_workspace_floats(int M);
 int vpt_rl_loss_launch(const VptRlLossArgs* a, float* totals, float* workspace, hipStream_t s);
+long vpt_ppg_aux_loss_workspace_floats(int M);
+int vpt_ppg_aux_loss_launch(const VptPpgAuxLossArgs* a, float* totals, float* workspace, hipStream_t s);
 int vpt_gae_launch(const VptGaeArgs* a, hipStream_t s);
 int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t s);
 long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid);

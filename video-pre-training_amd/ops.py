@@ -71,7 +71,7 @@ def _call(name, meta, *args, fmt="bf16", label=None):
 
 WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
 WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
-WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD, WS_RL_LOSS = 11, 12, 13
+WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD, WS_RL_LOSS, WS_PPG_AUX_LOSS = 11, 12, 13, 14
 FULL_ATTENTION_MAX_T = 160      # the mask="none" attention kernels' longest window (forward and backward)
 
 
@@ -1090,6 +1090,52 @@ def rl_loss(lp_buttons, lp_camera, act_buttons, act_camera, old_log_prob, advant
           ptr(act_buttons), ptr(act_camera), ptr(old_log_prob), ptr(advantage), ptr(value), ctypes.c_int64(stride), ptr(value_target), ptr(vnorm),
           ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws), m, nb, nc, ldz, f(clip), f(kl_coef), f(entropy_coef), f(value_coef),
           f(temperature), f(scale), _stream(), fmt=fmt)
+    return dz, frame_out, totals
+
+
+def ppg_aux_loss(lp_buttons, lp_camera, old_buttons, old_camera, ldz, scale, *, value=None, value_target=None, vnorm=None, weight=None,
+                 clone_coef=1.0, value_coef=0.5, temperature=1.0, dtype=torch.bfloat16, want_dz=True, want_frames=True, want_totals=True):
+    """The loss of PPG's auxiliary phase in one sweep (vpt_ppg_aux_loss) -> (dz | None, frame_out | None, totals | None): clone_coef x
+    KL(pi_old || pi) + value_coef x (v - normalised target)^2, per frame, weighted mean over the frames.  The KL's expectation runs over the stored
+    snapshot old_* (the opposite direction of rl_loss's KL(pi || prior)).
+    lp_* / old_* fp32 [M, n] log-probs (both old rows are required); value, value_target, vnorm, weight as rl_loss takes them (value = None: no value
+    term).  dz: 16-bit [M, ldz], ldz >= nb + nc + 1 = clone_coef (p - o) scale w / temperature per head -- the gradient for a teacher of mass exactly
+    1; the exact one is p S - o -- then 2 value_coef (v - t^) scale w, then zeros (a zero-weight row: exact zeros); frame_out fp32 [M, 8] = D_b, D_c,
+    (v - t^)^2, S_b, S_c, w, w > 0, 0 (unweighted; S = sum exp(old), the teacher's mass); totals fp32 [8] = sum_r w frame_out[r, :5], sum w, rows
+    with w > 0, 0.  `scale` carries 1 / sum w (and the fp16 loss scale); the temperature is applied by the kernel.  At most 65536 rows with totals.
+    tests/ppg_loss_ref.py is the fp64 host reference."""
+    for t, nme in ((lp_buttons, "lp_buttons"), (lp_camera, "lp_camera"), (old_buttons, "old_buttons"), (old_camera, "old_camera"),
+                   (value_target, "value_target"), (vnorm, "vnorm"), (weight, "weight")):
+        _chk(t, torch.float32, nme)
+    if old_buttons is None or old_camera is None:
+        raise ValueError("ppg_aux_loss: both old_buttons and old_camera (the snapshot's log-probs) are required")
+    if lp_buttons.dim() != 2 or lp_camera.dim() != 2:
+        raise ValueError("ppg_aux_loss: log-probs must be [M, classes]")
+    m, nb = lp_buttons.shape
+    nc = lp_camera.shape[1]
+    if lp_camera.shape[0] != m or any(t.numel() != m for t in (weight, value, value_target) if t is not None):
+        raise ValueError(f"ppg_aux_loss: every per-frame tensor must have {m} rows")
+    if old_buttons.shape != lp_buttons.shape or old_camera.shape != lp_camera.shape:
+        raise ValueError("ppg_aux_loss: the snapshot's log-probs must have the policy's shapes")
+    stride = 0
+    if value is not None:
+        if not value.is_cuda or value.dtype != torch.float32 or value.dim() != 1 or (m > 1 and value.stride(0) < 1):
+            raise ValueError("ppg_aux_loss: value must be a 1-D fp32 GPU tensor (or view) with a positive stride")
+        if value_target is None or vnorm is None or vnorm.numel() != 2:
+            raise ValueError("ppg_aux_loss: the value term needs value_target [M] and vnorm [2] = (mean, std) on the device")
+        stride = value.stride(0) if m > 1 else 1
+    if not temperature > 0:
+        raise ValueError("ppg_aux_loss: temperature must be positive")
+    dt, fmt = _fmt(dtype=dtype)
+    dev = lp_buttons.device
+    dz = torch.empty(m, ldz, dtype=dt, device=dev) if want_dz else None
+    frame_out = torch.empty(m, 8, dtype=torch.float32, device=dev) if want_frames else None
+    totals = torch.empty(8, dtype=torch.float32, device=dev) if want_totals else None
+    ws = _workspace(WS_PPG_AUX_LOSS, m, device=dev, fmt=fmt) if want_totals else None
+    f = ctypes.c_float
+    _call("vpt_ppg_aux_loss", dict(bytes=(8.0 * (nb + nc) + (2.0 * ldz if want_dz else 0.0)) * m), ptr(lp_buttons), ptr(lp_camera), ptr(old_buttons),
+          ptr(old_camera), ptr(value), ctypes.c_int64(stride), ptr(value_target), ptr(vnorm), ptr(weight), ptr(dz), ptr(frame_out), ptr(totals), ptr(ws),
+          m, nb, nc, ldz, f(clone_coef), f(value_coef), f(temperature), f(scale), _stream(), fmt=fmt)
     return dz, frame_out, totals
 
 

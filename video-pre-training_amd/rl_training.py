@@ -11,7 +11,15 @@ auxiliary KL to the frozen pre-trained policy, per frame r of a [B, T] chunk:
 
 KL and H are summed over the two heads.  One launch (ops.rl_loss) turns the head log-probs into dz, the per-frame records and their totals; everything
 below the head logits is BCTrainer's: forward_saving, backward_from(value_grads=True), the fused Adam launch and the fp16 loss scaling.  Advantages come
-from ops.gae (one launch per rollout).  Data-parallel steps and logit masks are not built."""
+from ops.gae (one launch per rollout).  Data-parallel steps and logit masks are not built.
+
+VPT's fine-tuning is PHASIC policy gradient: after every few policy-phase iterations an auxiliary ("sleep") phase keeps fitting the value head on the
+stored returns through the whole shared trunk, the policy held at a snapshot taken just before the phase (policy_snapshot):
+
+    L_r  = clone_coef KL(pi_old || pi) + aux_value_coef (v - normalise(target))^2
+
+One network, one value head (PPG's single-network variant, what the released models are).  aux_step is that phase's step: one launch
+(ops.ppg_aux_loss, one sweep over the two rows of log-probs) between the same forward and backward, the same Adam moments and step count."""
 import math
 from typing import Optional
 
@@ -23,16 +31,20 @@ from .training import BCTrainer
 
 METRICS = ("loss", "pg_loss", "kl_buttons", "kl_camera", "entropy_buttons", "entropy_camera", "value_loss", "clip_frac", "approx_kl", "ratio_mean",
            "weight_sum", "frames")
+AUX_METRICS = ("loss", "clone_kl_buttons", "clone_kl_camera", "value_loss", "teacher_mass_buttons", "teacher_mass_camera", "weight_sum", "frames")
 
 
 class PPOTrainer(BCTrainer):
     def __init__(self, policy, clip: float = 0.2, kl_coef: float = 0.0, entropy_coef: float = 0.0, value_coef: float = 0.5, gamma: float = 0.999,
-                 lam: float = 0.95, normalize_advantages: bool = True, update_value_normalizer: bool = True, **bc_kwargs):
+                 lam: float = 0.95, normalize_advantages: bool = True, update_value_normalizer: bool = True, clone_coef: float = 1.0,
+                 aux_value_coef: Optional[float] = None, **bc_kwargs):
         """clip: the ratio's clipping range; kl_coef: weight of KL(pi || prior) (needs prior_lp in every call when > 0); entropy_coef: entropy bonus;
         value_coef: weight of the squared value error in normalised space; gamma, lam: advantages()'s discount and GAE lambda.
         normalize_advantages: (A - mean) / (std + 1e-8) over the weighted frames of the call (the population std).
         update_value_normalizer: every loss_and_grads / step first feeds its value targets to the value head's EWMA normaliser, as the reference's
         ScaledMSEHead.loss does in training mode (lib/scaled_mse_head.py:43 -> lib/normalize_ewma.py:37-52), then normalises with the new statistics.
+        clone_coef, aux_value_coef: the auxiliary phase's weights of KL(pi_old || pi) and of the squared value error (aux_step; None: value_coef);
+        nothing outside the aux_* methods reads them.
         bc_kwargs: BCTrainer's arguments (lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, episode_starts,
         max_grad_norm -- global-norm gradient clipping, off by default; see there).
         The value head's Linear trains here (BCTrainer excludes it: it has no gradient under the BC loss)."""
@@ -40,6 +52,8 @@ class PPOTrainer(BCTrainer):
         self.clip, self.kl_coef, self.entropy_coef, self.value_coef = float(clip), float(kl_coef), float(entropy_coef), float(value_coef)
         self.gamma, self.lam = float(gamma), float(lam)
         self.normalize_advantages, self.update_value_normalizer = bool(normalize_advantages), bool(update_value_normalizer)
+        self.clone_coef = float(clone_coef)
+        self.aux_value_coef = self.value_coef if aux_value_coef is None else float(aux_value_coef)
 
     def _is_trainable(self, name: str) -> bool:
         if name.startswith("value_head.linear."):
@@ -236,5 +250,132 @@ class PPOTrainer(BCTrainer):
         loss, grads, state_out = self.loss_and_grads(img_u8, first, state_in, act_buttons, act_camera, old_log_prob, advantage, value_target,
                                                      prior_lp=prior_lp, frame_weight=frame_weight, metrics=metrics, unscaled=False,
                                                      micro_batches=micro_batches)
+        loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._global_frames), img_u8.device, metrics)
+        return loss, state_out
+
+    # ---- the auxiliary ("sleep") phase of phasic policy gradient ("The auxiliary phase") ---------------------------------------
+    @torch.no_grad()
+    def policy_snapshot(self, img_u8, first, state_in):
+        """pi_old of an auxiliary phase: the trainer's OWN policy through its inference forward (prior_logprobs applied to self.policy)
+        -> (lp_buttons [M, nb], lp_camera [M, nc], state_out), fp32 (64 x 128 frames: 287 MB).  Taken once per phase, before the first aux_step; the
+        tensors do not follow the weights afterwards.  Take it under the same logit masks as the steps that use it."""
+        return self.prior_logprobs(self.policy, img_u8, first, state_in)
+
+    def _aux_inputs(self, img_u8, old_lp, value_target, frame_weight, global_weight=None):
+        """Validation + flattening shared by aux_loss_and_grads and aux_evaluate -> dict of [M] / [M, n] device tensors, w / wsum."""
+        self._single_rank()
+        if old_lp is None or len(old_lp) != 2 or old_lp[0] is None or old_lp[1] is None:
+            raise ValueError("PPOTrainer: the auxiliary phase needs old_lp = (lp_buttons, lp_camera) of the snapshot (policy_snapshot)")
+        m = img_u8.shape[0] * img_u8.shape[1]
+        w, wsum = None, float(m)
+        if frame_weight is not None:
+            w, wsum = self._checked_weights(frame_weight, img_u8)
+            if wsum == 0 and global_weight is None:
+                raise ValueError("frame_weight: every weight is zero (the loss sum w L / sum w is undefined)")
+        if global_weight is not None:
+            wsum = float(global_weight)
+        ob, oc = (q.reshape(m, -1).to(torch.float32).contiguous() for q in old_lp)
+        if ob.shape[1] != self.engine.n_buttons or oc.shape[1] != self.engine.n_camera:
+            raise ValueError(f"old_lp must hold [{m}, {self.engine.n_buttons}] and [{m}, {self.engine.n_camera}] log-probs, got {tuple(ob.shape)} and {tuple(oc.shape)}")
+        return dict(m=m, w=w, wsum=wsum, ob=ob, oc=oc, target=self._per_frame(value_target, m, img_u8.device, "value_target"))
+
+    def _aux_value_norm(self, target, w, update: bool):
+        """(mean, std) as a device pair; update=True first feeds the targets to the normaliser (whatever the policy phase's switch says)."""
+        if update:
+            nrm = self.policy.value_head.normalizer
+            nrm.update(target.reshape(-1, *nrm.running_mean.shape), weight=w)
+        return self._value_norm(target, w, update=False)
+
+    def _aux_loss_of(self, totals):
+        """The weighted mean loss from ops.ppg_aux_loss's totals; a term whose coefficient is 0 is left out (not multiplied by 0), as in the kernel."""
+        loss = torch.zeros((), dtype=torch.float32, device=totals.device)
+        if self.clone_coef != 0:
+            loss = loss + self.clone_coef * (totals[0] + totals[1])
+        if self.aux_value_coef != 0:
+            loss = loss + self.aux_value_coef * totals[2]
+        return loss / totals[5]
+
+    def _fill_aux_metrics(self, metrics: dict, totals, frame_out, bsz: int, t: int):
+        """totals [8] + the per-frame records -> the AUX_METRICS dict; device arithmetic only."""
+        ws = totals[5]
+        metrics.update(loss=self._aux_loss_of(totals), clone_kl_buttons=totals[0] / ws, clone_kl_camera=totals[1] / ws, value_loss=totals[2] / ws,
+                       teacher_mass_buttons=totals[3] / ws, teacher_mass_camera=totals[4] / ws, weight_sum=ws, frames=totals[6],
+                       frame_out=frame_out.view(bsz, t, 8))
+
+    def _aux_loss_and_backward(self, S, f, vnorm, scale):
+        """ops.ppg_aux_loss on a saving forward's log-probs and the backward behind it -> (grads, totals [8], records [M, 8], state_out)."""
+        nb, nc = self.engine.n_buttons, self.engine.n_camera
+        dz, frame_out, totals = ops.ppg_aux_loss(S["lp_b"], S["lp_c"], f["ob"], f["oc"], S["ldz"], scale, value=S["logits"][:, nb + nc],
+                                                 value_target=f["target"], vnorm=vnorm, weight=f["w"], clone_coef=self.clone_coef,
+                                                 value_coef=self.aux_value_coef, temperature=self.engine.cfg["temperature"], dtype=self.dtype)
+        return self.backward_from(S, dz, value_grads=True), totals, frame_out, S["state_out"]
+
+    @torch.no_grad()
+    def aux_loss_and_grads(self, img_u8, first, state_in, old_lp, value_target, *, frame_weight=None, metrics: Optional[dict] = None,
+                           unscaled: bool = True, global_weight: Optional[float] = None, micro_batches: int = 1,
+                           update_value_normalizer: bool = False):
+        """Forward (saving activations) + the fused auxiliary loss + backward.  Returns (loss, grads dict incl. value_head.linear.*, state_out).
+            L_r = clone_coef (KL_buttons + KL_camera)(pi_old || pi) + aux_value_coef (v - normalise(target))^2,   loss = sum w_r L_r / sum w_r
+        old_lp: (lp_buttons, lp_camera) of the snapshot on the same frames (policy_snapshot), [M, n] or [B, T, n]; value_target: [B, T], the stored
+        returns.  frame_weight, unscaled, global_weight, micro_batches: as loss_and_grads takes them (the scale and the (mean, std) pair are computed
+        once for the whole batch, old_lp is cut by rows).  update_value_normalizer: feed the targets to the value normaliser first -- off by
+        default, the policy phase has already seen these targets.  metrics: a dict this call fills with AUX_METRICS + frame_out fp32 [B, T, 8]
+        (D_b, D_c, (v - t^)^2, S_b, S_c, w, w > 0, 0): device tensors, nothing synchronises.
+        The gradient of the clone term is p - pi_old, exact for a snapshot whose mass is 1 (teacher_mass_* report it)."""
+        rows = self.micro_batch_rows(img_u8.shape[0], micro_batches) if micro_batches != 1 else None
+        f = self._aux_inputs(img_u8, old_lp, value_target, frame_weight, global_weight)
+        bsz, t = img_u8.shape[:2]
+        if rows is None:
+            S = self.forward_saving(img_u8, first, state_in)
+            vnorm = self._aux_value_norm(f["target"], f["w"], update_value_normalizer)
+            scale, self._global_frames = self._loss_gradient_scale(f["wsum"])
+            g, totals, frame_out, state_out = self._aux_loss_and_backward(S, f, vnorm, scale)
+        else:
+            vnorm = self._aux_value_norm(f["target"], f["w"], update_value_normalizer)
+            scale, self._global_frames = self._loss_gradient_scale(f["wsum"])
+            first = torch.as_tensor(first)
+
+            def run(k, lo, hi):
+                fk = {q: (x[lo * t:hi * t] if isinstance(x, torch.Tensor) else x) for q, x in f.items()}
+                S = self.forward_saving(img_u8[lo:hi], first[lo:hi], self._tree_rows(state_in, lo, hi))
+                return self._aux_loss_and_backward(S, fk, vnorm, scale)
+
+            g, totals, frame_out, states = self._accumulated_window(rows, run)
+            state_out = self._tree_cat_rows(states)
+        self._aux_totals = totals
+        loss = self._aux_loss_of(totals)
+        if metrics is not None:
+            self._fill_aux_metrics(metrics, totals, frame_out, bsz, t)
+        if unscaled and self.scaled:
+            self._unscale_(g, self._global_frames)
+        return loss, g, state_out
+
+    @torch.no_grad()
+    def aux_evaluate(self, img_u8, first, state_in, old_lp, value_target, *, frame_weight=None):
+        """Forward-only auxiliary loss and metrics of a [B, T] chunk -> (metrics dict as aux_loss_and_grads fills it, state_out): the inference
+        forward + ops.ppg_aux_loss without dz.  The value normaliser is NOT updated."""
+        f = self._aux_inputs(img_u8, old_lp, value_target, frame_weight)
+        self.policy._ensure_packed()
+        eng = self.engine
+        bsz, t = img_u8.shape[:2]
+        m = bsz * t
+        out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
+        lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
+        vnorm = self._value_norm(f["target"], f["w"], update=False)
+        _, frame_out, totals = ops.ppg_aux_loss(lp_b, lp_c, f["ob"], f["oc"], 0, 0.0, value=out["vpred"].reshape(m), value_target=f["target"], vnorm=vnorm,
+                                                weight=f["w"], clone_coef=self.clone_coef, value_coef=self.aux_value_coef,
+                                                temperature=eng.cfg["temperature"], dtype=self.dtype, want_dz=False)
+        metrics: dict = {}
+        self._fill_aux_metrics(metrics, totals, frame_out, bsz, t)
+        return metrics, out["state_out"]
+
+    @torch.no_grad()
+    def aux_step(self, img_u8, first, state_in, old_lp, value_target, *, frame_weight=None, metrics: Optional[dict] = None, micro_batches: int = 1,
+                 update_value_normalizer: bool = False):
+        """One optimiser step of the auxiliary phase on a [B, T] chunk.  Returns (loss, state_out).  The Adam moments, the step count, the
+        max_grad_norm clip and the loss-scale bookkeeping are step()'s own (TrainerBase._optimizer_tail): one optimiser, as in single-network PPG."""
+        self._need_optimizer_state()
+        loss, grads, state_out = self.aux_loss_and_grads(img_u8, first, state_in, old_lp, value_target, frame_weight=frame_weight, metrics=metrics,
+                                                         unscaled=False, micro_batches=micro_batches, update_value_normalizer=update_value_normalizer)
         loss, _ = self._optimizer_tail(loss, grads, self.grad_unscale(self._global_frames), img_u8.device, metrics)
         return loss, state_out
