@@ -480,6 +480,21 @@ int vpt_idm_loss(const float* lp_buttons, const float* lp_camera, const int64_t*
                  const float* weight, void* dz, float* frame_out, float* totals, float* workspace,
                  int M, int gb, int nb, int gc, int nc, int ldz, float scale, void* stream);
 
+/* Backward of the IDM's grouped log-softmax heads for an ARBITRARY incoming gradient -- what torch autograd hands to the outputs of
+ * InverseActionPolicy.forward when the caller writes its own loss through pi_head.logprob / entropy / kl_divergence (lib/action_head.py:136-184: a
+ * CategoricalActionHead of shape (groups, classes) is `groups` independent log-softmaxes of logits / temperature).  lp_buttons fp32 [M][gb][nb],
+ * lp_camera fp32 [M][gc][nc] (the forward's log-probs); g_buttons / g_camera = d loss / d log-prob in the same shapes, either may be NULL (= zeros:
+ * that head's block of dz is zero).  Per group, with log-probs l_j, incoming g_j and n classes, in fp32 without contraction:
+ *   s = ((g_0 + g_1) + ...) + g_{n-1},  p_j = expf(l_j),  dz_j = ((g_j - p_j s) * (1 / temperature)) * grad_scale,  rounded once to the operand format.
+ * mask_* (uint8, the log-probs' shapes, optional): the forward's availability masks -- a masked logit was overwritten with the constant LOG0, so its
+ * dz is 0 (its g still counts in s).  dz: 16-bit [M][ldz], ldz >= gb nb + gc nc, in the column order of the two head matrices concatenated
+ * ([group][class], buttons first), further columns zero; every element is written.  grad_scale: as vpt_heads_logprob_backward's.  No reduction
+ * crosses a lane: the same inputs give the same bits.  Returns -1 for M <= 0, a non-positive temperature, a group or class count below 1 or a
+ * short ldz. */
+int vpt_grouped_logprob_backward(const float* lp_buttons, const float* lp_camera, const float* g_buttons, const float* g_camera,
+                                 const uint8_t* mask_buttons, const uint8_t* mask_camera, void* dz,
+                                 int M, int gb, int nb, int gc, int nc, int ldz, float temperature, float grad_scale, void* stream);
+
 /* ---- reinforcement-learning fine-tuning of the cloned policy (the third stage of the method; the reference ships no RL training script, only the
  * pieces such a loss is made of: the heads' logprob / entropy / kl_divergence, lib/action_head.py:176-203,252-275, and the value head) ---- */
 

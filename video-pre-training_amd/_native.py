@@ -75,6 +75,7 @@ SIGNATURES = {
     "vpt_gae": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P],
     "vpt_full_attention_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_heads_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],
+    "vpt_grouped_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],
     "vpt_layernorm_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vpt_gate_cast": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_column_sum": [_P, _P, _P, _I, _I, _I, _P],

@@ -263,6 +263,56 @@ extern "C" int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t stream
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same backward for the inverse-dynamics model's heads (lib/action_head.py:136-184: a CategoricalActionHead of shape (groups, classes) is
+// `groups` independent log-softmaxes): gb nb-way button groups and gc nc-way camera groups per frame, an ARBITRARY incoming gradient g = dL/dlp
+// (what torch autograd hands to InverseActionPolicy.forward's outputs).  One element, with l, g the group's n log-probs and incoming gradients:
+//   s = ((g_0 + g_1) + ...) + g_{n-1}     p_j = expf(l_j)     dz_j = ((g_j - p_j s) * (1 / T)) * grad_scale     (fp32, no contraction)
+// rounded once to the operand format; a masked element (its logit was the constant LOG0) stores 0 -- its g still counts in s, as in autograd.
+// Shaped like vpt_idm_loss_kernel: one wavefront per frame, lane c owns columns c, c + 64, ... of the two head matrices concatenated ([group][class],
+// buttons first) and sums its own group serially (n <= 11 in the released heads: the g values come from L1).  No LDS, no barrier, no cross-lane
+// traffic, no atomics: the same inputs give the same bits.
+__device__ __forceinline__ float grouped_lp_bwd_elem(const float* l, const float* g, const uint8_t* mask, int i, int n, float inv_temp, float grad_scale) {
+#pragma clang fp contract(off)
+  const int base = (i / n) * n;
+  float s = g[base];
+  for (int c = 1; c < n; ++c) s = s + g[base + c];
+  if (mask && !mask[i]) return 0.f;
+  const float p = expf(l[i]);
+  const float d = g[i] - p * s;
+  return (d * inv_temp) * grad_scale;
+}
+
+__global__ __launch_bounds__(256) void vpt_grouped_lp_bwd_kernel(VptGroupedLpBwdArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= a.M) return;
+  const int nbt = a.gb * a.nb, nct = a.gc * a.nc;
+  const float* lb = a.lp_buttons + (size_t)row * nbt;
+  const float* lc = a.lp_camera + (size_t)row * nct;
+  const float* gb = a.g_buttons ? a.g_buttons + (size_t)row * nbt : nullptr;
+  const float* gc = a.g_camera ? a.g_camera + (size_t)row * nct : nullptr;
+  const uint8_t* mb = a.mask_buttons ? a.mask_buttons + (size_t)row * nbt : nullptr;
+  const uint8_t* mc = a.mask_camera ? a.mask_camera + (size_t)row * nct : nullptr;
+  vpt_op16* dz = a.dz + (size_t)row * a.ldz;
+  for (int i = lane; i < a.ldz; i += 64) {
+    float v = 0.f;
+    if (i < nbt) {
+      if (gb) v = grouped_lp_bwd_elem(lb, gb, mb, i, a.nb, a.inv_temp, a.grad_scale);
+    } else if (i < nbt + nct) {
+      if (gc) v = grouped_lp_bwd_elem(lc, gc, mc, i - nbt, a.nc, a.inv_temp, a.grad_scale);
+    }
+    dz[i] = (vpt_op16)v;
+  }
+}
+
+extern "C" int vpt_grouped_lp_bwd_launch(const VptGroupedLpBwdArgs* a, hipStream_t stream) {
+  if (a->M <= 0 || a->gb <= 0 || a->nb <= 0 || a->gc <= 0 || a->nc <= 0) return -1;
+  if (a->ldz < a->gb * a->nb + a->gc * a->nc) return -1;
+  hipLaunchKernelGGL(vpt_grouped_lp_bwd_kernel, dim3((a->M + 3) / 4), dim3(256), 0, stream, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------------------------------------
 // out_bf16[M][ldo] = (mask > 0 ? x : 0), columns >= N zero: ReLU gate + cast + K-padding of a GEMM A operand
 __global__ __launch_bounds__(256) void vpt_gate_cast_kernel(VptGateCastArgs a) {
   const size_t total = (size_t)a.M * a.ldo;

@@ -690,6 +690,21 @@ int vpt_heads_logprob_backward(const float* lp_buttons, const float* lp_camera, 
   CHECK_LAUNCH(vpt_heads_bwd_launch(&a, (hipStream_t)stream), "vpt_heads_logprob_backward");
 }
 
+int vpt_grouped_logprob_backward(const float* lp_buttons, const float* lp_camera, const float* g_buttons, const float* g_camera,
+                                 const uint8_t* mask_buttons, const uint8_t* mask_camera, void* dz,
+                                 int M, int gb, int nb, int gc, int nc, int ldz, float temperature, float grad_scale, void* stream) {
+  if (!lp_buttons || !lp_camera || !dz) return fail(-1, "vpt_grouped_logprob_backward: null log-probs / dz");
+  if (M <= 0) return fail(-1, "vpt_grouped_logprob_backward: M must be positive");
+  if (gb < 1 || nb < 1 || gc < 1 || nc < 1) return fail(-1, "vpt_grouped_logprob_backward: group and class counts must be at least 1");
+  if (!(temperature > 0.f)) return fail(-1, "vpt_grouped_logprob_backward: temperature must be positive");
+  if (ldz < gb * nb + gc * nc) return fail(-1, "vpt_grouped_logprob_backward: ldz < gb * nb + gc * nc");
+  VptGroupedLpBwdArgs a = {};
+  a.lp_buttons = lp_buttons; a.lp_camera = lp_camera; a.g_buttons = g_buttons; a.g_camera = g_camera;
+  a.mask_buttons = mask_buttons; a.mask_camera = mask_camera;
+  a.dz = (vpt_op16*)dz; a.M = M; a.gb = gb; a.nb = nb; a.gc = gc; a.nc = nc; a.ldz = ldz; a.inv_temp = 1.0f / temperature; a.grad_scale = grad_scale;
+  CHECK_LAUNCH(vpt_grouped_lp_bwd_launch(&a, (hipStream_t)stream), "vpt_grouped_logprob_backward");
+}
+
 int vpt_layernorm_backward(const float* x, const float* gain, const float* dy, const float* dx_add, float* dx,
                            float* dgain, float* dbias, float* partials, int M, int D, int relu_in, void* stream) {
   if (!partials) return fail(-1, "vpt_layernorm_backward: partials workspace is required");

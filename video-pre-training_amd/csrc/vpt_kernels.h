@@ -409,6 +409,19 @@ struct VptHeadsBwdArgs {   // generic backward of the two log-softmax heads + th
   float inv_temp;          // 1 / temperature
 };
 
+struct VptGroupedLpBwdArgs {   // the same backward for the IDM's grouped heads: gb nb-way + gc nc-way independent log-softmax groups per frame
+  const float* lp_buttons; // [M][gb][nb] log-probabilities (forward output)
+  const float* lp_camera;  // [M][gc][nc]
+  const float* g_buttons;  // optional [M][gb][nb]: incoming d loss / d log-prob (NULL = zeros: the head's block of dz is zero)
+  const float* g_camera;   // optional [M][gc][nc]
+  const uint8_t* mask_buttons;  // optional, the log-probs' shapes: 0 = the logit was replaced by the constant LOG0 in the forward
+  const uint8_t* mask_camera;   //   (lib/action_head.py:170-171): no gradient reaches it
+  vpt_op16* dz;            // [M][ldz]: d loss / d (the two heads' logits, [group][class], buttons first), further columns zero
+  float grad_scale;        // multiplies every written value (the fp16 lift; 1 otherwise)
+  int M, gb, nb, gc, nc, ldz;
+  float inv_temp;          // 1 / temperature
+};
+
 struct VptGateCastArgs {
   const float* x;          // [M][ldx]
   const vpt_op16* mask;    // optional [M][ldm]
@@ -527,6 +540,7 @@ int vpt_gae_launch(const VptGaeArgs* a, hipStream_t s);
 int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t s);
 long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid);
 int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);
+int vpt_grouped_lp_bwd_launch(const VptGroupedLpBwdArgs* a, hipStream_t s);
 int vpt_ln_bwd_launch(const VptLnBwdArgs* a, hipStream_t s);
 int vpt_gate_cast_launch(const VptGateCastArgs* a, hipStream_t s);
 int vpt_colsum_launch(const VptColsumArgs* a, hipStream_t s);

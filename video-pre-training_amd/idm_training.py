@@ -13,7 +13,12 @@ train_cnn=True is the first stage of the VPT method, training the IDM itself: th
 (cnn_training.CnnTrainingMixin, one copy of the launch order) with stack 0 fed by the temporal conv's output: there `firstconv` is a normed 3x3 conv on
 128 x 128 pixels, its dgrad returns dx0, and ops.conv3d_t5_backward turns (image, x0, dx0) into the temporal conv's weight and bias gradient.
 
-NOT built: data-parallel IDM steps, an autograd boundary for the IDM, and chunk streams for the CNN backward (one stream).
+The autograd boundary: a gradient-enabled `InverseActionPolicy.forward` is one autograd node (lib/policy.py:_IDMForwardFn) over forward_saving and
+backward_from of an IDMTrainer(optimizer_state=False) the policy keeps; the incoming gradients of the two grouped log-prob tensors become dz in one launch
+(ops.grouped_logprob_backward).  Any loss written through pi_head.logprob / entropy / kl_divergence then trains the IDM with `loss.backward()` and a torch
+optimizer; IDMTrainer.step stays the fast path for the plain NLL (fused loss, one-launch Adam).
+
+NOT built: data-parallel IDM steps, and chunk streams for the CNN backward (one stream).
 
 The trunk's saving forward and backward, the optimiser state and the loss-scale bookkeeping are trainer_base.TrainerBase's, shared with BCTrainer.
 The backward runs on the HIP kernels of the BC step (trainer_base.linear_backward, ops.layernorm_backward, ops.gate_cast, ops.column_sum_,
@@ -58,6 +63,9 @@ class IDMTrainer(TrainerBase):
         defaults to 256 (1 = off in bf16), the loss gradient is written as loss_scale / temperature x (softmax - one-hot) per frame, the optimiser
         launch un-scales, an overflowed step is skipped on the device, the scale halves then and doubles after `scale_growth_interval` clean steps."""
         self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm)
+        # the autograd boundary's counterpart of loss_scale (lib/policy.py:_IDMForwardFn.backward), as BCTrainer's: where the largest incoming
+        # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow the boundary detects
+        self.autograd_lift, self.autograd_overflows = 256.0, 0
         if self.train_cnn and not self.fused_pool:
             raise RuntimeError("IDMTrainer(train_cnn=True) needs the pool-fused forward (ops.conv3x3_pool_argmax): at 128 x 128 only the pooled entry of "
                                "the conv backward is built -- unset VPT_BC_FUSED_POOL=0")
@@ -111,13 +119,16 @@ class IDMTrainer(TrainerBase):
 
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def forward_saving(self, img_u8) -> dict:
+    def forward_saving(self, img_u8, mask: Optional[dict] = None) -> dict:
         """IDMEngine.forward with what the backward needs kept from the dense layer's pre-activation output `d` (fp32 [M, 256]) onward.  The frozen
         part in front of it runs exactly as the engine runs it (ops.conv3d_t5 per whole window, the CNN + dense layer in cnn_chunk pieces, nothing
         kept); behind it the same launches with the same tilings and split-K choice (the engine's, never the row count's), so the log-probs
         S["lp_b"] [M, 20, 2] / S["lp_c"] [M, 2, 11] equal IDMEngine.forward's bit for bit.
         train_cnn=True: the same chunks through the saving CNN forward (x0 and every CNN activation kept in S["cnn_saved"]; no `n` / dense folds, so
-        the log-probs equal the engine's to the parity bounds only)."""
+        the log-probs equal the engine's to the parity bounds only).
+        mask: {"buttons": bool [B, T, 20, 2], "camera": bool [B, T, 2, 11]} (either entry optional), as IDMEngine.forward takes it: False -> the logit is
+        the constant LOG0.  Kept in S["mask"] as {"buttons" / "camera": uint8 [M, G, n] or None} for the backward (None when no mask was given, and
+        then the launches are the unmasked call's)."""
         eng = self.engine
         self.policy._ensure_packed()
         cfg, w = eng.cfg, eng.w
@@ -147,12 +158,15 @@ class IDMTrainer(TrainerBase):
         d = outs[0] if len(outs) == 1 else torch.cat(outs, 0)                        # [M, 256] pre-ReLU dense output: a constant of the backward
         trunk = self._trunk_forward_saving(d, lambda l, p, qkv: (ops.full_attention(qkv, bsz, t, heads, hid, dtype=dt), {}), **lin)
         _, lb = ops.layernorm(trunk["x_trunk"], w["final.g"], w["final.b"], relu_in=True, out_f32=False, dtype=dt)          # ReLU, then final_ln; no lastlayer
-        lps = {}
+        lps, kept = {}, None
         for h, (groups, n) in (("buttons", eng.button_shape), ("camera", eng.camera_shape)):
             z, _ = ops.linear(lb, w[h + ".w"], groups * n, bias=w[h + ".b"], **lin)
-            lps[h] = action_heads(z, ((h, 0, groups, n),), bsz, t, cfg["temperature"])[h].view(m, groups, n)
+            lps[h] = action_heads(z, ((h, 0, groups, n),), bsz, t, cfg["temperature"], mask)[h].view(m, groups, n)
+        if mask is not None:
+            kept = {h: (mask[h].reshape(m, groups, n).to(torch.uint8).contiguous() if mask.get(h) is not None else None)
+                    for h, (groups, n) in (("buttons", eng.button_shape), ("camera", eng.camera_shape))}
         return dict(trunk, m=m, bsz=bsz, t=t, dev=img_u8.device, d=d, lb=lb,
-                    lp_b=lps["buttons"], lp_c=lps["camera"], cnn_saved=cnn_saved, cnn_step=step)
+                    lp_b=lps["buttons"], lp_c=lps["camera"], mask=kept, cnn_saved=cnn_saved, cnn_step=step)
 
     def _attention_backward(self, S, l, datt, g):
         """Mask "none": no memory, no relative-position bias -- nothing of the attention itself is trained."""

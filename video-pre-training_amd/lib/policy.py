@@ -196,6 +196,52 @@ class ScaledMSEHead(nn.Module):
         return self.normalizer.normalize(x)
 
 
+def _take_saved(ctx):
+    """The saved activations of a boundary node, once: a second backward raises (the activations are released to the backward as it runs)."""
+    S = ctx.S
+    if S is None:
+        raise RuntimeError("the policy's activations were already consumed by a backward pass (retain_graph is not supported)")
+    ctx.S = None
+    return S
+
+
+def _lift_scale(eng, incoming):
+    """The factor the incoming gradients are multiplied by on their way into the 16-bit gradient buffers (both boundary nodes).  1 in bf16.
+    fp16 operands: the 16-bit gradient buffers need the incoming gradients lifted into IEEE half's range (a mean over M frames arrives as 1 / M
+    per element).  Power of two, so un-scaling the fp32 results (_unlift_) is exact.  `autograd_lift` (256 to start with) is where the largest
+    incoming element is placed; an overflow halves it.  -> None when the INCOMING gradient is inf / nan (the caller's loss, not our lift): no
+    gradient from this backward, counted, warned, and the lift stays where it is -- halving it would not have helped."""
+    if not eng.scaled:
+        return 1.0
+    gmax = max([float(x.abs().max()) for x in incoming if x is not None and x.numel()] or [0.0])
+    if not math.isfinite(gmax):
+        import warnings
+        eng.autograd_overflows += 1
+        warnings.warn("fp16 backward received a non-finite gradient: this backward returns no gradients", RuntimeWarning)
+        return None
+    return 2.0 ** math.floor(math.log2(eng.autograd_lift / gmax)) if gmax > 0.0 else 1.0
+
+
+def _unlift_(eng, g, scale) -> bool:
+    """The lifted gradients `g` (name -> fp32 tensor) -> those of the caller's loss, in place -> True; False when an IEEE-half buffer overflowed.
+    GradScaler semantics at the autograd boundary: the caller's optimizer (th.optim.Adam in the reference's loop, behavioural_cloning.py:117-122)
+    must never see the inf / nan a half overflow in dz / dacc / dx16 leaves behind.  On overflow the backward contributes NO gradient (every input
+    gradient None: an optimizer skips parameters whose .grad is None, an accumulation loop simply misses this sample), warns, and the next
+    backward lifts less."""
+    from .. import ops
+    if eng.scaled and int(ops.grads_nonfinite(list(g.values())).item()):
+        import warnings
+        eng.autograd_lift = max(1.0, eng.autograd_lift * 0.5)
+        eng.autograd_overflows += 1
+        warnings.warn(f"fp16 backward overflowed (gradient lift 2^{math.log2(scale):.0f}): this backward returns no gradients; "
+                      f"the next one lifts to {eng.autograd_lift:g}", RuntimeWarning)
+        return False
+    if scale != 1.0:
+        for t_ in g.values():
+            t_.mul_(1.0 / scale)
+    return True
+
+
 class _PolicyForwardFn(torch.autograd.Function):
     """The differentiable boundary: MinecraftAgentPolicy.forward as ONE autograd node whose backward is the hand-written
     HIP backward of training.py (every layer, CNN included).  That is what lets the reference's own training loop --
@@ -224,51 +270,61 @@ class _PolicyForwardFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_b, g_c, g_v, *g_state):
         from .. import ops
-        S, eng = ctx.S, ctx.grad_engine
-        if S is None:
-            raise RuntimeError("the policy's activations were already consumed by a backward pass (retain_graph is not supported)")
-        ctx.S = None
+        S, eng = _take_saved(ctx), ctx.grad_engine
         m = S["m"]
         flat2 = lambda g_, n_: None if g_ is None else g_.reshape(m, n_).float().contiguous()
         nb, nc = eng.engine.n_buttons, eng.engine.n_camera
         gv = None if g_v is None else g_v.reshape(m).float().contiguous()
+        none = (None,) * (7 + len(ctx.names))
         with torch.no_grad():
             gb, gc = flat2(g_b, nb), flat2(g_c, nc)
-            scale = 1.0
-            if eng.scaled:
-                # fp16 operands: the 16-bit gradient buffers need the incoming gradients lifted into IEEE half's range (a mean
-                # over M frames arrives as 1 / M per element).  Power of two, so un-scaling the fp32 results below is exact.
-                # `autograd_lift` (256 to start with) is where the largest incoming element is placed; an overflow halves it.
-                gmax = max([float(x.abs().max()) for x in (gb, gc, gv) if x is not None and x.numel()] or [0.0])
-                if not math.isfinite(gmax):
-                    # the INCOMING gradient is inf / nan (the caller's loss, not our lift): no gradient from this backward, counted, and
-                    # the lift stays where it is -- halving it would not have helped
-                    import warnings
-                    eng.autograd_overflows += 1
-                    warnings.warn("fp16 backward received a non-finite gradient: this backward returns no gradients", RuntimeWarning)
-                    return (None,) * (7 + len(ctx.names))
-                if gmax > 0.0:
-                    scale = 2.0 ** math.floor(math.log2(eng.autograd_lift / gmax))
+            scale = _lift_scale(eng, (gb, gc, gv))
+            if scale is None:
+                return none
             dz = ops.heads_logprob_backward(S["lp_b"], S["lp_c"], gb, gc, gv, S["ldz"], eng.engine.cfg["temperature"],
                                             mask_buttons=S["mask"]["buttons"], mask_camera=S["mask"]["camera"], dtype=eng.dtype, grad_scale=scale)
             g = eng.backward_from(S, dz, value_grads=gv is not None)
-            if eng.scaled:
-                # GradScaler semantics at the autograd boundary: the caller's optimizer (th.optim.Adam in the reference's loop,
-                # behavioural_cloning.py:117-122) must never see the inf / nan a half overflow in dz / dacc / dx16 leaves behind.
-                # On overflow this backward contributes NO gradient (every input gradient None: an optimizer skips parameters
-                # whose .grad is None, an accumulation loop simply misses this sample), warns, and the next backward lifts less.
-                if int(ops.grads_nonfinite(list(g.values())).item()):
-                    import warnings
-                    eng.autograd_lift = max(1.0, eng.autograd_lift * 0.5)
-                    eng.autograd_overflows += 1
-                    warnings.warn(f"fp16 backward overflowed (gradient lift 2^{math.log2(scale):.0f}): this backward returns no gradients; "
-                                  f"the next one lifts to {eng.autograd_lift:g}", RuntimeWarning)
-                    return (None,) * (7 + len(ctx.names))
-            if scale != 1.0:
-                for t_ in g.values():
-                    t_.mul_(1.0 / scale)
+            if not _unlift_(eng, g, scale):
+                return none
         grads = tuple(g[n].reshape(shape) if n in g else None for n, shape in zip(ctx.names, ctx.param_shapes))
         return (None, None, None, None, None, None, None) + grads
+
+
+class _IDMForwardFn(torch.autograd.Function):
+    """_PolicyForwardFn's twin for the inverse-dynamics model: InverseActionPolicy.forward as ONE autograd node over IDMTrainer.forward_saving /
+    backward_from (idm_training.py), so that a loss written through pi_head.logprob / entropy / kl_divergence (lib/action_head.py:176-203) trains
+    the IDM with `loss.backward(); optimizer.step()`.  The incoming gradients of the two grouped log-prob tensors become dz in one launch
+    (ops.grouped_logprob_backward).  Mask "none" has no recurrent state: nothing else is returned."""
+
+    @staticmethod
+    def forward(ctx, grad_engine, img, mask, names, *params):
+        S = grad_engine.forward_saving(img, mask=mask)
+        bsz, t = S["bsz"], S["t"]
+        (gb, nb), (gc, nc) = grad_engine.engine.button_shape, grad_engine.engine.camera_shape
+        ctx.S, ctx.grad_engine, ctx.names = S, grad_engine, names
+        ctx.param_shapes = [p.shape for p in params]
+        ctx.set_materialize_grads(False)     # a head the loss does not use arrives as None: its block of dz is zero
+        return S["lp_b"].view(bsz, t, gb, nb), S["lp_c"].view(bsz, t, gc, nc)
+
+    @staticmethod
+    def backward(ctx, g_b, g_c):
+        from .. import ops
+        S, eng = _take_saved(ctx), ctx.grad_engine
+        like = lambda g_, lp: None if g_ is None else g_.reshape(lp.shape).float().contiguous()
+        none = (None,) * (4 + len(ctx.names))
+        with torch.no_grad():
+            gb, gc = like(g_b, S["lp_b"]), like(g_c, S["lp_c"])
+            scale = _lift_scale(eng, (gb, gc))
+            if scale is None:
+                return none
+            mask = S["mask"] or {}
+            dz = ops.grouped_logprob_backward(S["lp_b"], S["lp_c"], gb, gc, eng.engine.cfg["temperature"], mask_buttons=mask.get("buttons"),
+                                              mask_camera=mask.get("camera"), dtype=eng.dtype, grad_scale=scale)
+            g = eng.backward_from(S, dz)
+            if not _unlift_(eng, g, scale):
+                return none
+        grads = tuple(g[n].reshape(shape) if n in g else None for n, shape in zip(ctx.names, ctx.param_shapes))
+        return (None, None, None, None) + grads
 
 
 class MinecraftAgentPolicy(nn.Module):
@@ -680,13 +736,20 @@ class InverseActionPolicy(nn.Module):
         bt, ct = action_space["buttons"], action_space["camera"]
         self._engine = IDMEngine(self._cfg, (bt.size, bt.eltype.n), (ct.size, ct.eltype.n), precision=precision)
         self._packed_key = None
+        self._grad_engines = {}
 
     @property
     def precision(self) -> str:
         return self._engine.precision
 
+    @property
+    def grad_overflows(self) -> int:
+        """How many backward passes through this model returned NO gradients (MinecraftAgentPolicy.grad_overflows).  Always 0 in bf16."""
+        return sum(e.autograd_overflows for e in self._grad_engines.values())
+
     def set_precision(self, precision: str):
         if precision != self._engine.precision:
+            self._grad_engines = {}
             old = self._engine
             self._engine = IDMEngine(self._cfg, old.button_shape, old.camera_shape, precision=precision)
             self._engine.adopt_sampler(old)
@@ -725,11 +788,28 @@ class InverseActionPolicy(nn.Module):
         img = obs["img"]
         if img.dtype != torch.uint8:
             raise TypeError("obs['img'] must be uint8 [B,T,128,128,3]")
+        if sample is None and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            # gradient-enabled call, as the reference's forward is: the log-probs join the autograd graph (_IDMForwardFn)
+            return (self._forward_differentiable(img, mask), None, None), state_in, {}
         out = self._engine.forward(img, mask=mask, sample=sample)
         pi_logits = {"buttons": out["buttons"], "camera": out["camera"]}
         extra = {k: out[k] for k in ("action", "action_log_prob") if k in out}
         # mask "none" / maxlen 0: the state passes through empty (lib/xf.py:366-391 with cache_keep_len = 0)
         return (pi_logits, None, None), state_in, extra
+
+    def _forward_differentiable(self, img, mask=None):
+        """Gradient-enabled call: IDMTrainer's saving forward, outputs attached to the autograd graph through _IDMForwardFn.  The CNN and the temporal
+        conv are trained (train_cnn) exactly when one of their parameters requires grad; with them frozen (`requires_grad_(False)`) the part in front
+        of the dense layer's output runs as in inference and the log-probs equal the no_grad forward's bit for bit.  Parameters the function does
+        not reach (`net.lastlayer.*`, the empty `b_nd`, a frozen CNN) get no gradient (None); `r_layer.*` gets exact zeros, as from IDMTrainer."""
+        from ..idm_training import IDMTrainer
+        named = list(self.named_parameters())
+        train_cnn = any(p.requires_grad for n, p in named if n.startswith(("net.conv3d_layer.", "net.img_process.cnn.")))
+        eng = self._grad_engines.get(train_cnn)
+        if eng is None:
+            eng = self._grad_engines[train_cnn] = IDMTrainer(self, train_cnn=train_cnn, optimizer_state=False)
+        lp_b, lp_c = _IDMForwardFn.apply(eng, img, mask, [n for n, _ in named], *[p for _, p in named])
+        return {"buttons": lp_b, "camera": lp_c}
 
     @torch.no_grad()
     def predict(self, obs, deterministic: bool = True, **kwargs):

@@ -1043,6 +1043,36 @@ def idm_loss(lp_buttons, lp_camera, act_buttons, act_camera, scale, weight=None,
     return dz, frame_out, totals
 
 
+def grouped_logprob_backward(lp_buttons, lp_camera, g_buttons, g_camera, temperature, mask_buttons=None, mask_camera=None, dtype=torch.bfloat16,
+                             grad_scale=1.0):
+    """Backward of the IDM's grouped log-softmax heads for arbitrary incoming gradients (vpt_grouped_logprob_backward) -> dz, 16-bit
+    [M, round_up(G_b n_b + G_c n_c, 64)] = d loss / d (the two heads' logits, [group][class], buttons first; padding: exact zeros).
+    lp_buttons fp32 [M, G_b, n_b], lp_camera fp32 [M, G_c, n_c]; g_* fp32 of the same shapes = d loss / d log-prob, or None (zeros: that head's block
+    of dz is zero); mask_* uint8 of the same shapes or None: the forward's availability masks (a masked element gets 0).  Per group
+    dz_j = ((g_j - exp(lp_j) sum_k g_k) / temperature) * grad_scale, rounded once.  The autograd boundary of lib/policy.py:_IDMForwardFn uses this; the
+    trainer's fast path is idm_loss."""
+    _chk(lp_buttons, torch.float32, "lp_buttons"); _chk(lp_camera, torch.float32, "lp_camera")
+    _chk(g_buttons, torch.float32, "g_buttons"); _chk(g_camera, torch.float32, "g_camera")
+    _chk(mask_buttons, torch.uint8, "mask_buttons"); _chk(mask_camera, torch.uint8, "mask_camera")
+    if lp_buttons.dim() != 3 or lp_camera.dim() != 3:
+        raise ValueError("grouped_logprob_backward: log-probs must be [M, groups, classes]")
+    m, gb, nb = lp_buttons.shape
+    gc, nc = lp_camera.shape[1:]
+    if lp_camera.shape[0] != m:
+        raise ValueError(f"grouped_logprob_backward: lp_camera must have {m} rows")
+    for t, ref, nme in ((g_buttons, lp_buttons, "g_buttons"), (mask_buttons, lp_buttons, "mask_buttons"), (g_camera, lp_camera, "g_camera"),
+                        (mask_camera, lp_camera, "mask_camera")):
+        if t is not None and tuple(t.shape) != tuple(ref.shape):
+            raise ValueError(f"grouped_logprob_backward: {nme} must be {tuple(ref.shape)}, got {tuple(t.shape)}")
+    dt, fmt = _fmt(dtype=dtype)
+    ldz = (gb * nb + gc * nc + 63) // 64 * 64
+    dz = torch.empty(m, ldz, dtype=dt, device=lp_buttons.device)
+    _call("vpt_grouped_logprob_backward", dict(bytes=(12.0 * (gb * nb + gc * nc) + 2.0 * ldz) * m), ptr(lp_buttons), ptr(lp_camera), ptr(g_buttons),
+          ptr(g_camera), ptr(mask_buttons), ptr(mask_camera), ptr(dz), m, gb, nb, gc, nc, ldz, ctypes.c_float(temperature), ctypes.c_float(grad_scale),
+          _stream(), fmt=fmt)
+    return dz
+
+
 def rl_loss(lp_buttons, lp_camera, act_buttons, act_camera, old_log_prob, advantage, ldz, scale, *, prior_buttons=None, prior_camera=None,
             value=None, value_target=None, vnorm=None, weight=None, clip=0.2, kl_coef=0.0, entropy_coef=0.0, value_coef=0.5, temperature=1.0,
             dtype=torch.bfloat16, want_dz=True, want_frames=True, want_totals=True):
