@@ -682,6 +682,20 @@ int vpt_idm_decode(const float* lp_buttons, const float* lp_camera, int64_t* but
 int vpt_clip_frames(const uint8_t* src_bgr, int frames, int height, int width, const int32_t* cursor_state, const uint8_t* cursor_bgr,
                     const double* cursor_alpha, int cursor_h, int cursor_w, uint8_t* dst_rgb, int out_height, int out_width, void* stream);
 
+/* ---- sequence-consistent frame augmentation (no reference counterpart: the reference trains on the loader's frames as they are) ---- */
+
+/* out[frames][9] = the nine uniforms in [0, 1) of each frame, a pure function of (seed, epoch, keys[f]): Philox4x32-10 with key (seed lo, seed hi),
+ * counter (draw >> 2, key lo, key hi, epoch), word draw & 3, u = (word >> 8) * 2^-24.  Draw order: hue, saturation, brightness, contrast, rotation,
+ * scale, shear, tx, ty.  Frames with equal keys (a recording's id) get equal draws, in whichever launch they appear. */
+int vpt_augment_uniforms(const int64_t* keys, float* out, long frames, uint64_t seed, uint32_t epoch, void* stream);
+/* dst[f] = frame src[f] (uint8 [frames][H][W][3]) under tables[f] (fp32 [frames][16]: colour matrix C[3][3] row-major, mean gain k, inverse map G[2][3]
+ * from an output pixel index (x, y) to a source pixel index):
+ *   v_c = bilinear taps of channel c at ((G00 x + G01 y) + G02, (G10 x + G11 y) + G12), 0 outside the frame;
+ *   out_c = (uint8) rint(min(max(((C[c][0] v_0 + C[c][1] v_1) + C[c][2] v_2) + k mu, 0), 255)),  mu = sum(77 R + 150 G + 29 B) / (256 H W) of the frame.
+ * Fixed fp32 arithmetic without fused multiply-adds (csrc/vpt_augment_pixel.h); no table contents make it read outside a frame (non-finite coordinates
+ * take the fill value).  H * W * 3 <= 65536 (the frame is staged in LDS), else -5.  dst may be src itself (in place); other overlaps are not supported. */
+int vpt_augment_frames(const uint8_t* src, const float* tables, uint8_t* dst, long frames, int H, int W, void* stream);
+
 /* ---- diagnostics ---- */
 
 /* Fill the LDS of every compute unit with NaN bit patterns (0x7fc07fc0: a NaN as fp32 and as either 16-bit operand format), enqueued on

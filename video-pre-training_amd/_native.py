@@ -92,6 +92,8 @@ SIGNATURES = {
     "vpt_masked_attention_step_inplace": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_act_epilogue": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P],
     "vpt_clip_frames": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P],
+    "vpt_augment_uniforms": [_P, _P, _L, ctypes.c_uint64, ctypes.c_uint32, _P],
+    "vpt_augment_frames": [_P, _P, _P, _L, _I, _I, _P],
     "vpt_debug_poison_lds": [_P],
     "vpt_episode_bounds": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vpt_masked_attention_forward_episodes": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],

@@ -793,6 +793,20 @@ int vpt_clip_frames(const uint8_t* src_bgr, int frames, int height, int width, c
   CHECK_LAUNCH(vpt_clip_launch(&a, (hipStream_t)stream), "vpt_clip_frames");
 }
 
+/* ---- sequence-consistent frame augmentation (vpt_augment.hip) ---- */
+int vpt_augment_uniforms(const int64_t* keys, float* out, long frames, uint64_t seed, uint32_t epoch, void* stream) {
+  if (!keys || !out) return fail(-1, "vpt_augment_uniforms: null pointer");
+  if (frames <= 0) return fail(-1, "vpt_augment_uniforms: frames must be positive");
+  CHECK_LAUNCH(vpt_augment_uniforms_launch(keys, out, frames, seed, epoch, (hipStream_t)stream), "vpt_augment_uniforms");
+}
+
+int vpt_augment_frames(const uint8_t* src, const float* tables, uint8_t* dst, long frames, int H, int W, void* stream) {
+  if (!src || !tables || !dst) return fail(-1, "vpt_augment_frames: null pointer");
+  if (frames <= 0 || H <= 0 || W <= 0) return fail(-1, "vpt_augment_frames: frames, H and W must be positive");
+  if ((long)H * W * 3 > 65536) return fail(-5, "vpt_augment_frames: a frame must fit the LDS staging (H * W * 3 <= 65536)");
+  CHECK_LAUNCH(vpt_augment_frames_launch(src, tables, dst, frames, H, W, (hipStream_t)stream), "vpt_augment_frames");
+}
+
 int vpt_debug_poison_lds(void* stream) {
   static unsigned long long optin_done = 0;
   const int bytes = 160 * 1024;

@@ -545,6 +545,8 @@ int vpt_ln_bwd_launch(const VptLnBwdArgs* a, hipStream_t s);
 int vpt_gate_cast_launch(const VptGateCastArgs* a, hipStream_t s);
 int vpt_colsum_launch(const VptColsumArgs* a, hipStream_t s);
 int vpt_clip_launch(const VptClipArgs* a, hipStream_t s);
+int vpt_augment_uniforms_launch(const int64_t* keys, float* out, long frames, uint64_t seed, uint32_t epoch, hipStream_t s);
+int vpt_augment_frames_launch(const uint8_t* src, const float* tables, uint8_t* dst, long frames, int H, int W, hipStream_t s);
 int vpt_attn_step_launch(const VptAttnArgs* a, const uint8_t* state_mask, const uint8_t* first, uint8_t* mask_out, float* kout, float* vout, int* done, hipStream_t s);
 int vpt_act_epilogue_launch(const int64_t* act_b, const int64_t* act_c, const float* lp_b, const float* lp_c, const float* logits, int ld, int vcol,
                             float scale, float shift, int64_t* keep, uint8_t* nan_flag, uint64_t* rng_state, int B, hipStream_t s);

@@ -36,7 +36,7 @@ class VideoLabels:
         return self.buttons.shape[0]
 
 
-def labelled_chunks(videos: Sequence[Tuple[torch.Tensor, VideoLabels]], n_rows: int, seq_len: int, drop_null: bool = True) -> Iterator[dict]:
+def labelled_chunks(videos: Sequence[Tuple[torch.Tensor, VideoLabels]], n_rows: int, seq_len: int, drop_null: bool = True, *, augment=None) -> Iterator[dict]:
     """[B = n_rows, T = seq_len] training chunks from labelled videos: a list of (frames uint8 [N,128,128,3], VideoLabels).
 
     Video i goes to row i % n_rows; a row plays its videos one after the other.  drop_null=True removes the null-labelled frames first, as the
@@ -49,7 +49,9 @@ def labelled_chunks(videos: Sequence[Tuple[torch.Tensor, VideoLabels]], n_rows: 
       weight       fp32  [B, T]   1 for a frame, 0 for padding (BCTrainer.step's `frame_weight`)
     A row that has run out of frames is padded as SequenceBatcher._padded_chunk pads: zero image, first = True, action indices 0,
     episode_id = -1, weight = 0.  Unlike the loader's protocol, which stops at the first empty lane, iteration goes on until EVERY row is
-    empty, so each kept frame of each video appears exactly once, in order.  Pure tensor logic: runs on whatever device the inputs are on."""
+    empty, so each kept frame of each video appears exactly once, in order.  Pure tensor logic: runs on whatever device the inputs are on.
+    augment: optional callable chunk dict -> chunk dict applied to every chunk (augment.FrameAugmenter: one image transform per video, keyed by
+    episode_id; padding frames stay as they are).  None: the chunks are what they were."""
     n_rows, seq_len = int(n_rows), int(seq_len)
     if n_rows < 1 or seq_len < 1:
         raise ValueError("labelled_chunks: n_rows and seq_len must be at least 1")
@@ -57,7 +59,8 @@ def labelled_chunks(videos: Sequence[Tuple[torch.Tensor, VideoLabels]], n_rows: 
     for i, (frames, lab) in enumerate(videos):
         if frames.dtype != torch.uint8 or frames.dim() != 4 or tuple(frames.shape[1:]) != (128, 128, 3) or frames.shape[0] != len(lab):
             raise ValueError(f"labelled_chunks: video {i}: frames must be uint8 [{len(lab)},128,128,3], got {frames.dtype} {tuple(frames.shape)}")
-    return _chunks(videos, n_rows, seq_len, bool(drop_null))
+    chunks = _chunks(videos, n_rows, seq_len, bool(drop_null))
+    return chunks if augment is None else (augment(c) for c in chunks)
 
 
 def _chunks(videos, n_rows, seq_len, drop_null):

@@ -1416,3 +1416,44 @@ def clip_frames(frames_bgr, cursor_state=None, cursor_bgr=None, cursor_alpha=Non
         _call("vpt_clip_frames", dict(bytes=float(f) * (h * w * 3 + oh * ow * 3)), ptr(frames_bgr), f, h, w, ptr(cursor_state), ptr(cursor_bgr), ptr(cursor_alpha),
               ch, cw, ptr(out), oh, ow, _stream())
     return out
+
+
+AUGMENT_MAX_FRAME_BYTES = 65536      # vpt_augment_frames stages a frame whole in LDS (csrc/vpt_augment_pixel.h: VPT_AUG_MAX_FRAME_BYTES)
+
+
+def augment_uniforms(keys, seed, epoch, fmt="bf16"):
+    """int64 keys [...] -> fp32 [keys.numel(), 9]: the nine uniforms in [0, 1) of every frame (vpt_augment_uniforms): Philox4x32-10, key = seed, counter =
+    (draw >> 2, key lo, key hi, epoch).  A pure function of (seed, epoch, key): equal keys give equal rows in whichever call they appear."""
+    _chk(keys, torch.int64, "keys")
+    n = keys.numel()
+    out = torch.empty(n, 9, dtype=torch.float32, device=keys.device)
+    if n:
+        _call("vpt_augment_uniforms", dict(bytes=44.0 * n), ptr(keys), ptr(out), n, ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF),
+              ctypes.c_uint32(int(epoch) & 0xFFFFFFFF), _stream(), fmt=fmt)
+    return out
+
+
+def augment_frames(img, tables, out=None, fmt="bf16"):
+    """uint8 frames [F,H,W,3] or [B,T,H,W,3] under fp32 tables [F,16] (colour matrix 3x3 row-major, mean gain, inverse affine map 2x3: include/vpt_hip.h)
+    -> uint8 frames of the same shape, one launch (vpt_augment_frames).  Fixed fp32 arithmetic: tests/augment_ref.py restates it bit for bit.
+    H * W * 3 <= 65536 (a frame is staged in LDS).  `out` may be `img` itself (in place); any other overlap is not supported."""
+    _chk(img, torch.uint8, "img"); _chk(tables, torch.float32, "tables")
+    if img.dim() not in (4, 5) or img.shape[-1] != 3:
+        raise ValueError("img must be [F, H, W, 3] or [B, T, H, W, 3]")
+    h, w = int(img.shape[-3]), int(img.shape[-2])
+    f = img.numel() // (h * w * 3) if h * w else 0
+    if h < 1 or w < 1:
+        raise ValueError("augment_frames: empty frames")
+    if h * w * 3 > AUGMENT_MAX_FRAME_BYTES:
+        raise ValueError(f"augment_frames: a frame of {h} x {w} x 3 bytes does not fit the LDS staging (H * W * 3 <= {AUGMENT_MAX_FRAME_BYTES})")
+    if tuple(tables.shape) != (f, 16) or tables.device != img.device:
+        raise ValueError(f"augment_frames: tables must be fp32 [{f}, 16] on {img.device}, got {tuple(tables.shape)} on {tables.device}")
+    if out is None:
+        out = torch.empty_like(img)
+    else:
+        _chk(out, torch.uint8, "out")
+        if tuple(out.shape) != tuple(img.shape) or out.device != img.device:
+            raise ValueError(f"augment_frames: out must be uint8 {tuple(img.shape)} on {img.device}, got {tuple(out.shape)} on {out.device}")
+    if f:
+        _call("vpt_augment_frames", dict(bytes=float(f) * (2 * h * w * 3 + 64)), ptr(img), ptr(tables), ptr(out), f, h, w, _stream(), fmt=fmt)
+    return out

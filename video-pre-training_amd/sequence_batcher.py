@@ -51,9 +51,12 @@ class SequenceBatcher:
     pad_last=True keeps that chunk instead: every chunk also carries `weight` fp32 [B, T] (BCTrainer's `frame_weight`; all ones for a full
     chunk), and when a lane runs dry the chunk in progress is completed with padding -- zero image, first = True, action indices 0,
     episode_id = -1, weight = 0 -- and returned if it holds at least one real item; the next iteration stops.  `dropped_frames` stays 0, and
-    only real items reach the action encoder."""
+    only real items reach the action encoder.
 
-    def __init__(self, loader, seq_len: int, action_encoder: Optional[Callable] = None, pad_last: bool = False):
+    augment: optional callable chunk dict -> chunk dict applied to every chunk before it is returned (augment.FrameAugmenter: one image transform
+    per recording, keyed by episode_id, so it holds across chunk edges; padding frames stay as they are).  None: the chunks are what they were."""
+
+    def __init__(self, loader, seq_len: int, action_encoder: Optional[Callable] = None, pad_last: bool = False, *, augment: Optional[Callable] = None):
         if int(seq_len) < 1:
             raise ValueError("seq_len must be at least 1")
         if getattr(loader, "to_numpy", False):
@@ -61,6 +64,7 @@ class SequenceBatcher:
         self.loader = loader
         self.seq_len = int(seq_len)
         self.pad_last = bool(pad_last)
+        self.augment = augment
         self.n_rows = loader.n_workers
         self.device = torch.device(loader._device)
         self._encode = action_encoder or default_action_encoder(self.device)
@@ -73,6 +77,10 @@ class SequenceBatcher:
         return self
 
     def __next__(self):
+        chunk = self._next_chunk()
+        return chunk if self.augment is None else self.augment(chunk)
+
+    def _next_chunk(self):
         if self._done:
             raise StopIteration()
         # lanes are served round-robin, one item at a time, exactly as the loader's own iteration serves them: a lane asks for its next
