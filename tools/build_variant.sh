@@ -1,6 +1,7 @@
 #!/bin/bash
 # Experiment builds of the conv kernel: build_variant.sh <name> <defines...>  ->  build/libvpt_<name>.so (bf16 library with
 # vpt_conv3x3.hip compiled with the given -D flags).  Run with VPT_HIP_LIB=... (see _native.py).
+# Forward-loop ablations (timing only): -DVPT_CONV_PROFILE -DVPT_CONV_FWD_ABLATE=1|2|4 (no weight DMA | no halo reloads | neither).
 set -e
 cd "$(dirname "$0")/../video-pre-training_amd"
 name=$1; shift

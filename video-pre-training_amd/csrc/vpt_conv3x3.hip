@@ -48,6 +48,16 @@
 #else
 #define CONV_ABLATE 0
 #endif
+// Timing-only ablations of the FORWARD main loop (wrong results; -DVPT_CONV_PROFILE builds only, chosen at compile time so that the unablated
+// loop carries no branch): -DVPT_CONV_FWD_ABLATE=1 no weight DMA inside the loop (stale weights), 2 no halo reloads (block 0's halo serves every
+// channel block), 4 both (MFMAs, fragment reads, waits and barriers only).  profiles/conv3x3_cycles.md has the table they gave.
+#if defined(VPT_CONV_PROFILE) && defined(VPT_CONV_FWD_ABLATE)
+#define FWD_NO_DMA (VPT_CONV_FWD_ABLATE == 1 || VPT_CONV_FWD_ABLATE == 4)
+#define FWD_NO_HALO (VPT_CONV_FWD_ABLATE == 2 || VPT_CONV_FWD_ABLATE == 4)
+#else
+#define FWD_NO_DMA 0
+#define FWD_NO_HALO 0
+#endif
 #define A_RS 80
 #define A_BYTES (324 * A_RS)            // 25920
 #define B_BYTES (3 * 128 * 64)          // 24576 per buffer (unpadded, swizzled)
@@ -356,6 +366,16 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   // residual), one slot per group; the step's barrier sits in front of its LAST group, which holds every fragment it needs and requests the
   // next step's first ones behind the barrier.
   // ====================================================================================================================
+  // Weight DMA piece of the forward loop: a BUFFER load to LDS (resource wrs over this channel tile's packed weights, the lane's 32-bit offset,
+  // step and piece in the scalar offset).  global_load_lds is a FLAT-encoded operation that the compiler's wait-count model books as a possible
+  // LDS access with out-of-order return: behind each piece every fragment wait of the loop degenerated to lgkmcnt(0), so the first MFMA of a
+  // group also waited for the fragment requested one instruction earlier, and each piece carried two 64-bit vector adds for its address.  The
+  // buffer form is counted in vmcnt alone: the loop's fragment waits stay COUNTED (lgkmcnt(7) .. (1)) and a piece costs scalar adds only.
+#define GLDS16(m_)                                                                                        \
+  do { if (POOL) { if (!FWD_NO_DMA) GLDS(m_); } else if ((m_) < NDMA && !FWD_NO_DMA)                      \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(bd_ + (m_) * (NWAVE * 1024)), 16, wvoff, \
+                                           (s_ + 1) * B_BYTES + (m_) * (NWAVE * 1024), 0, 0); } while (0)
+#define XA16(m_) do { if (!FWD_NO_HALO) XA(m_); } while (0)
 #define HALO_WR16(m_) do { if ((m_) < NA - 1 || a_lastok) *(u32x4*)(smem + a_l0 + (m_) * H16_STR) = ((a_inside >> (m_)) & 1u) ? areg[m_] : zero4; } while (0)
 #define PA(j_, dy_, dx_) fp[j_] = *(const __attribute__((address_space(3))) op16x8*)((((dx_) & 1) ? aLo : aLe) + (((j_) + (dy_)) * 18 + (dx_)) * A_RS)
 #define WB(tap_, u_, boff_) fw[(u_) & 1] = *(const __attribute__((address_space(3))) op16x8*)((((u_) & 1) ? bW1 : bW0) + (boff_) + (tap_) * (128 * 64) + ((u_) >> 1) * (32 * 64))
@@ -399,29 +419,29 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   do {                                                                                                    \
     const int s_ = (cb_) * 3 + (dy_);                                                                     \
     const int boff_ = (s_ & 1) * B_BYTES, noff_ = B_BYTES - boff_;                                        \
-    const op16_t* wp_ = wbase + (size_t)(s_ + 1) * 12288;                                                 \
+    const op16_t* wp_ = wbase + (size_t)(s_ + 1) * 12288;     /* (the pool-fused modes' global_load_lds) */ \
     unsigned char* bd_ = bdst + noff_;                                                                    \
     const unsigned cbo_ = (unsigned)((cb_) + 1) * (unsigned)HW * 64u; /* bytes; uniform */                \
     if (LAST) {                                                                                           \
       TAP16(M16A, dy_, 0, NOP_(), NOP_(), NOP_(), NOP_());                                                \
     } else {                                                                                              \
-      TAP16(M16A, dy_, 0, GLDS(0), GLDS(1), GLDS(2), GLDS(3));                                            \
+      TAP16(M16A, dy_, 0, GLDS16(0), GLDS16(1), GLDS16(2), GLDS16(3));                                          \
     }                                                                                                     \
     if (PRE_A) {                                                                                          \
-      TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), do { XA(0); XA(1); } while (0), XA(2));                       \
-      G16(M16A, 0, WB(2, 1, boff_), do { XA(3); XA(4); } while (0));                                      \
-      G16(M16A, 1, WB(2, 2, boff_), XA(5));                                                               \
+      TAP16(M16A, dy_, 1, GLDS16(4), GLDS16(5), do { XA16(0); XA16(1); } while (0), XA16(2));             \
+      G16(M16A, 0, WB(2, 1, boff_), do { XA16(3); XA16(4); } while (0));                                  \
+      G16(M16A, 1, WB(2, 2, boff_), XA16(5));                                                             \
       G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
       if (NA == 6) WAIT_BARRIER(6); else WAIT_BARRIER(5);                                                 \
     } else if ((PRE_R) && HAS_RES) {                                                                      \
-      TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), XR16(0), NOP_());                                             \
+      TAP16(M16A, dy_, 1, GLDS16(4), GLDS16(5), XR16(0), NOP_());                                           \
       G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
       G16(M16A, 1, WB(2, 2, boff_), NOP_());                                                              \
       G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
       WAIT_BARRIER(2);   /* row 0 x 2 blocks */                                                                                      \
     } else {                                                                                              \
       if (LAST) TAP16(M16A, dy_, 1, NOP_(), NOP_(), NOP_(), NOP_());                                      \
-      else TAP16(M16A, dy_, 1, GLDS(4), GLDS(5), NOP_(), NOP_());                                         \
+      else TAP16(M16A, dy_, 1, GLDS16(4), GLDS16(5), NOP_(), NOP_());                                       \
       G16(M16A, 0, WB(2, 1, boff_), NOP_());                                                              \
       G16(M16A, 1, WB(2, 2, boff_), NOP_());                                                              \
       G16(M16A, 2, WB(2, 3, boff_), NOP_());                                                              \
@@ -429,8 +449,8 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     }                                                                                                     \
     if (WR_A) {   /* the halo of the next channel block replaces the current one: second barrier before its first read */ \
       _Pragma("unroll") for (int m_ = 0; m_ < 4; ++m_) {                                                  \
-        HALO_WR16(m_); SB();                                                                              \
-        if (m_ + 4 < NA) HALO_WR16(m_ + 4);                                                               \
+        if (!FWD_NO_HALO) HALO_WR16(m_); SB();                                                            \
+        if (m_ + 4 < NA && !FWD_NO_HALO) HALO_WR16(m_ + 4);                                                         \
         SB(); if (m_ == 0) M16A(0, 3); else if (m_ == 1) M16A(1, 3); else if (m_ == 2) M16A(2, 3); else M16A(3, 3); SB();                                                                        \
       }                                                                                                   \
       WAIT_BARRIER(0);                                                                                    \
@@ -576,6 +596,10 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   op16x8 fa[2][4], fb[2][2];   // dgrad: two fragment register sets
   const op16_t* resp = a.res;
   op16x8 fp[8], fw[2];         // forward: the current tap's 8 pixel fragments, a double-buffered weight fragment
+  // forward weight DMA (GLDS16): resource over this channel tile's NCB * 9 packed tap tiles of 8 KB -- built from kernel arguments and the block index
+  // only, so it lives in scalar registers; reads beyond it would return zeros (none: step s + 1 <= 3 NCB - 1 ends at the resource's last byte)
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.wpk + (size_t)nt * NCB * 9 * 4096), 0, NCB * 9 * 8192, 0x00020000);
+  const int wvoff = (w * 64 + lane) * 16;
 
   if (TRACE && (FWD16 || tid == 0)) t_trace[1] = wall_clock64();
   if constexpr (FWD16) {
