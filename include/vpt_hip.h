@@ -31,7 +31,9 @@ const char* vpt_version(void);
  * list or a symbol is renamed or removed (adding entry points does not raise it); a caller compares it with the VPT_HIP_ABI it
  * was built against before the first call -- _native.py does -- instead of finding out through a mis-typed argument.
  * History: 3 = round 3 (vpt_adam_step_multi + skip_flag, vpt_heads_logprob_backward + grad_scale, vpt_gate_cast renamed);
- * 4 = round 4 (vpt_conv3x3_forward_tiled rejects tiling 0; vpt_action_head_forward takes a counter-based noise source). */
+ * 4 = round 4 (vpt_conv3x3_forward_tiled rejects tiling 0; vpt_action_head_forward takes a counter-based noise source).
+ * Entry points added under 5 without a change of number, by the rule above: vpt_grad_accumulate_multi, vpt_augment_*, vpt_rollout_record / _reward (a
+ * binding that requires one of them refuses a library that lacks it by name, _native.py). */
 #define VPT_HIP_ABI 5
 int vpt_abi_version(void);
 /* "bf16" (libvpt_hip.so, the default) or "fp16" (libvpt_hip_f16.so: the same sources built with -DVPT_OPERAND_F16): the format
@@ -555,6 +557,31 @@ int vpt_ppg_aux_loss(const float* lp_buttons, const float* lp_camera, const floa
  * one lane per sequence walking back over t, in this order of fp32 operations without contraction: a float32 host loop reproduces it bit for bit. */
 int vpt_gae(const float* reward, const float* value, const uint8_t* first, const float* last_value, const uint8_t* next_first,
             float* adv, float* ret, int B, int T, float gamma, float lam, void* stream);
+
+/* ---- rollout collection for RL fine-tuning (no reference counterpart: the reference ships no RL loop) ---- */
+
+/* One acting step of B environments into column t of [B][T] rollout buffers, one launch: what MinecraftAgentPolicy.act (lib/policy.py:307-331) hands out
+ * per step -- the frame, its `first` flag, the sampled action indices, their summed log-prob and the de-normalised value -- lands where the training step
+ * reads it.  img uint8 [B][frame_bytes] -> img_buf [B][T][frame_bytes] with 16-byte vector loads and stores (frame_bytes % 16 == 0, both pointers 16-byte
+ * aligned; a 128 x 128 x 3 frame is 3072 vectors); first uint8 [B] -> first_buf [B][T] (stored as 0 / 1).  The four scalar inputs are read through ELEMENT
+ * strides (environment b's value is at [b * stride], stride >= 0), so the views of vpt_act_epilogue's packed record (stride 4 int64s / 8 floats) and
+ * contiguous arrays (stride 1) both go in without a copy.  nan_flag uint8 [1] is STICKY: a NaN among the stored log-probs stores 1 (a plain byte store, no
+ * atomic: every writer writes the same value); no launch clears it -- the caller zeroes it when a rollout begins and reads it once when it ends.
+ * t outside [0, T) is rejected with -1; B <= 65535. */
+int vpt_rollout_record(const uint8_t* img, const uint8_t* first, const int64_t* act_buttons, const int64_t* act_camera, const float* log_prob,
+                       const float* vpred, int64_t stride_buttons, int64_t stride_camera, int64_t stride_log_prob, int64_t stride_vpred,
+                       uint8_t* img_buf, uint8_t* first_buf, int64_t* act_buttons_buf, int64_t* act_camera_buf, float* old_log_prob_buf, float* vpred_buf,
+                       uint8_t* nan_flag, int B, int T, int t, int64_t frame_bytes, void* stream);
+
+/* The environment's answer to step t, one lane per environment: reward fp32 [B], done uint8 [B] (the NEXT frame starts an episode).
+ *   reward_buf[b][t] = r;  R = ep_return[b] + r;  n = ep_length[b] + 1;
+ *   done:      done_return[b][t] = R, done_length[b][t] = n, ep_return[b] = 0, ep_length[b] = 0;
+ *   otherwise: done_return[b][t] = 0, done_length[b][t] = 0, ep_return[b] = R, ep_length[b] = n.
+ * ep_return fp32 [B] / ep_length int32 [B] are the running totals of the episode in progress; the caller zeroes them once and keeps them across rollouts,
+ * so an episode that spans two rollouts reports its whole return.  One fp32 add per lane per step, no contraction, no cross-lane reduction: a float32 host
+ * loop reproduces every output bit for bit; totals over a rollout are the caller's sums over done_return / done_length. */
+int vpt_rollout_reward(const float* reward, const uint8_t* done, float* reward_buf, float* done_return, int32_t* done_length, float* ep_return,
+                       int32_t* ep_length, int B, int T, int t, void* stream);
 
 /* ---- backward of the IMPALA CNN (behavioural_cloning.py:117-119 obtains these from torch autograd) ---- */
 

@@ -73,6 +73,8 @@ SIGNATURES = {
     "vpt_rl_loss": [_P] * 9 + [ctypes.c_int64] + [_P] * 7 + [_I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P],
     "vpt_ppg_aux_loss": [_P] * 5 + [ctypes.c_int64] + [_P] * 7 + [_I, _I, _I, _I, _F, _F, _F, _F, _P],
     "vpt_gae": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P],
+    "vpt_rollout_record": [_P] * 6 + [ctypes.c_int64] * 4 + [_P] * 7 + [_I, _I, _I, ctypes.c_int64, _P],
+    "vpt_rollout_reward": [_P] * 7 + [_I, _I, _I, _P],
     "vpt_full_attention_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_heads_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],
     "vpt_grouped_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],

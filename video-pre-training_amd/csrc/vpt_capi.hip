@@ -666,6 +666,37 @@ int vpt_gae(const float* reward, const float* value, const uint8_t* first, const
   CHECK_LAUNCH(vpt_gae_launch(&a, (hipStream_t)stream), "vpt_gae");
 }
 
+int vpt_rollout_record(const uint8_t* img, const uint8_t* first, const int64_t* act_buttons, const int64_t* act_camera, const float* log_prob,
+                       const float* vpred, int64_t stride_buttons, int64_t stride_camera, int64_t stride_log_prob, int64_t stride_vpred,
+                       uint8_t* img_buf, uint8_t* first_buf, int64_t* act_buttons_buf, int64_t* act_camera_buf, float* old_log_prob_buf, float* vpred_buf,
+                       uint8_t* nan_flag, int B, int T, int t, int64_t frame_bytes, void* stream) {
+  if (!img || !first || !act_buttons || !act_camera || !log_prob || !vpred) return fail(-1, "vpt_rollout_record: null input");
+  if (!img_buf || !first_buf || !act_buttons_buf || !act_camera_buf || !old_log_prob_buf || !vpred_buf || !nan_flag) return fail(-1, "vpt_rollout_record: null buffer");
+  if (B <= 0 || T <= 0) return fail(-1, "vpt_rollout_record: B and T must be positive");
+  if (t < 0 || t >= T) return fail(-1, "vpt_rollout_record: t must be in [0, T)");
+  if (frame_bytes <= 0 || (frame_bytes & 15)) return fail(-1, "vpt_rollout_record: frame_bytes must be a positive multiple of 16");
+  if (((uintptr_t)img | (uintptr_t)img_buf) & 15) return fail(-1, "vpt_rollout_record: img and img_buf must be 16-byte aligned");
+  if (stride_buttons < 0 || stride_camera < 0 || stride_log_prob < 0 || stride_vpred < 0) return fail(-1, "vpt_rollout_record: negative stride");
+  VptRolloutRecordArgs a = {};
+  a.img = img; a.first = first; a.act_buttons = act_buttons; a.act_camera = act_camera; a.log_prob = log_prob; a.vpred = vpred;
+  a.stride_buttons = (long)stride_buttons; a.stride_camera = (long)stride_camera; a.stride_log_prob = (long)stride_log_prob; a.stride_vpred = (long)stride_vpred;
+  a.img_buf = img_buf; a.first_buf = first_buf; a.act_buttons_buf = act_buttons_buf; a.act_camera_buf = act_camera_buf;
+  a.old_log_prob_buf = old_log_prob_buf; a.vpred_buf = vpred_buf; a.nan_flag = nan_flag;
+  a.frame_vec = (long)(frame_bytes >> 4); a.B = B; a.T = T; a.t = t;
+  CHECK_LAUNCH(vpt_rollout_record_launch(&a, (hipStream_t)stream), "vpt_rollout_record");
+}
+
+int vpt_rollout_reward(const float* reward, const uint8_t* done, float* reward_buf, float* done_return, int32_t* done_length, float* ep_return,
+                       int32_t* ep_length, int B, int T, int t, void* stream) {
+  if (!reward || !done || !reward_buf || !done_return || !done_length || !ep_return || !ep_length) return fail(-1, "vpt_rollout_reward: null pointer");
+  if (B <= 0 || T <= 0) return fail(-1, "vpt_rollout_reward: B and T must be positive");
+  if (t < 0 || t >= T) return fail(-1, "vpt_rollout_reward: t must be in [0, T)");
+  VptRolloutRewardArgs a = {};
+  a.reward = reward; a.done = done; a.reward_buf = reward_buf; a.done_return = done_return; a.done_length = done_length;
+  a.ep_return = ep_return; a.ep_length = ep_length; a.B = B; a.T = T; a.t = t;
+  CHECK_LAUNCH(vpt_rollout_reward_launch(&a, (hipStream_t)stream), "vpt_rollout_reward");
+}
+
 int vpt_full_attention_backward(const float* qkv, const float* dout, float* dqkv, float* dkv_slab,
                                 int B, int t, int heads, int hid, int ld, void* stream) {
   if (!qkv || !dout || !dqkv) return fail(-1, "vpt_full_attention_backward: null pointer");

@@ -387,6 +387,36 @@ struct VptGaeArgs {         // generalised advantage estimation, one lane per se
   float gamma, lam;
 };
 
+struct VptRolloutRecordArgs {   // one acting step of B environments into column t of [B][T] rollout buffers (vpt_rollout_record_kernel)
+  const uint8_t* img;      // [B][frame_vec * 16] the step's frames, 16-byte aligned
+  const uint8_t* first;    // [B] the frame starts an episode
+  const int64_t* act_buttons;   // element b at [b * stride_buttons]
+  const int64_t* act_camera;    // element b at [b * stride_camera]
+  const float* log_prob;   // element b at [b * stride_log_prob]: the sampled action's summed log-prob
+  const float* vpred;      // element b at [b * stride_vpred]: the de-normalised value
+  long stride_buttons, stride_camera, stride_log_prob, stride_vpred;
+  uint8_t* img_buf;        // [B][T][frame_vec * 16]
+  uint8_t* first_buf;      // [B][T]
+  int64_t* act_buttons_buf;     // [B][T]
+  int64_t* act_camera_buf;      // [B][T]
+  float* old_log_prob_buf; // [B][T]
+  float* vpred_buf;        // [B][T]
+  uint8_t* nan_flag;       // [1] sticky: 1 once a stored log-prob was NaN
+  long frame_vec;          // 16-byte vectors per frame
+  int B, T, t;
+};
+
+struct VptRolloutRewardArgs {   // the environment's answer to step t, one lane per environment (vpt_rollout_reward_kernel)
+  const float* reward;     // [B]
+  const uint8_t* done;     // [B] the NEXT frame starts an episode
+  float* reward_buf;       // [B][T]
+  float* done_return;      // [B][T] the finished episode's return where done, else 0
+  int32_t* done_length;    // [B][T] its length in steps where done, else 0
+  float* ep_return;        // [B] running return of the episode in progress (persists across rollouts)
+  int32_t* ep_length;      // [B] its length so far
+  int B, T, t;
+};
+
 struct VptFullAttnBwdArgs { // backward of vpt_attn_kernel with causal = 0 (mask "none", no memory, no bias): vpt_full_attn_bwd_kernel
   const float* qkv;        // forward projections [B*t][ld]: Q | K | V
   const float* dout;       // [B*t][hid]
@@ -537,6 +567,8 @@ int vpt_rl_loss_launch(const VptRlLossArgs* a, float* totals, float* workspace, 
 long vpt_ppg_aux_loss_workspace_floats(int M);
 int vpt_ppg_aux_loss_launch(const VptPpgAuxLossArgs* a, float* totals, float* workspace, hipStream_t s);
 int vpt_gae_launch(const VptGaeArgs* a, hipStream_t s);
+int vpt_rollout_record_launch(const VptRolloutRecordArgs* a, hipStream_t s);
+int vpt_rollout_reward_launch(const VptRolloutRewardArgs* a, hipStream_t s);
 int vpt_full_attn_bwd_launch(const VptFullAttnBwdArgs* a, hipStream_t s);
 long vpt_full_attn_bwd_dkv_floats(int B, int t, int hid);
 int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);

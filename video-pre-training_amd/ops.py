@@ -1188,6 +1188,81 @@ def gae(reward, value, first, last_value, next_first, gamma=0.999, lam=0.95):
     return adv, ret
 
 
+def _chk_strided(x, dtype, b, name):
+    """A per-environment scalar input of rollout_record: `b` elements along ONE axis with a non-negative element stride (a contiguous [B] / [B, 1] tensor
+    or a column view of a packed record) -> its element stride."""
+    if not x.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if x.dtype != dtype:
+        raise TypeError(f"{name}: expected {dtype}, got {x.dtype}")
+    if x.numel() != b:
+        raise ValueError(f"{name}: expected one value per environment ({b}), got {tuple(x.shape)}")
+    strides = [s for n, s in zip(x.shape, x.stride()) if n != 1]
+    if len(strides) > 1 or any(s < 0 for s in strides):
+        raise ValueError(f"{name}: the {b} values must lie along one axis, got shape {tuple(x.shape)} with strides {x.stride()}")
+    return strides[0] if strides else 1
+
+
+def rollout_record(img, first, act_buttons, act_camera, log_prob, vpred, t, img_buf, first_buf, act_buttons_buf, act_camera_buf, old_log_prob_buf,
+                   vpred_buf, nan_flag):
+    """One acting step of B environments into column t of the [B, T] rollout buffers, in place, one launch (vpt_rollout_record).  img uint8 [B, ...] ->
+    img_buf uint8 [B, T, ...]; first bool / uint8 [B] -> first_buf (bool / uint8 [B, T]); act_buttons, act_camera int64, log_prob, vpred fp32, one value
+    per environment each, contiguous or strided along one axis (the views of unpack_act_keep go in as they are) -> act_*_buf int64, old_log_prob_buf,
+    vpred_buf fp32 [B, T].  nan_flag uint8 [1]: set to 1 by a NaN log-prob, never cleared here.  tests/rollout_ref.py is the numpy twin."""
+    _chk(img, torch.uint8, "img"); _chk(img_buf, torch.uint8, "img_buf")
+    _chk(act_buttons_buf, torch.int64, "act_buttons_buf"); _chk(act_camera_buf, torch.int64, "act_camera_buf")
+    _chk(old_log_prob_buf, torch.float32, "old_log_prob_buf"); _chk(vpred_buf, torch.float32, "vpred_buf"); _chk(nan_flag, torch.uint8, "nan_flag")
+    if img_buf.dim() < 3 or img.dim() != img_buf.dim() - 1:
+        raise ValueError(f"rollout_record: img must be [B, ...] and img_buf [B, T, ...], got {tuple(img.shape)} and {tuple(img_buf.shape)}")
+    b, t_len = img_buf.shape[:2]
+    if img.shape[0] != b or img.shape[1:] != img_buf.shape[2:]:
+        raise ValueError(f"rollout_record: img {tuple(img.shape)} does not hold {b} frames of img_buf {tuple(img_buf.shape)}")
+    t = int(t)
+    if not 0 <= t < t_len:
+        raise ValueError(f"rollout_record: t = {t} is outside the horizon [0, {t_len})")
+    frame_bytes = img[0].numel()
+    if frame_bytes % 16 or img.data_ptr() % 16 or img_buf.data_ptr() % 16:
+        raise ValueError("rollout_record: frames must be a multiple of 16 bytes and 16-byte aligned")
+    first8 = first.view(torch.uint8) if first.dtype == torch.bool else first
+    fbuf8 = first_buf.view(torch.uint8) if first_buf.dtype == torch.bool else first_buf
+    _chk(first8, torch.uint8, "first"); _chk(fbuf8, torch.uint8, "first_buf")
+    if first8.numel() != b:
+        raise ValueError(f"rollout_record: first must hold {b} flags, got {tuple(first.shape)}")
+    for x, name in ((fbuf8, "first_buf"), (act_buttons_buf, "act_buttons_buf"), (act_camera_buf, "act_camera_buf"), (old_log_prob_buf, "old_log_prob_buf"),
+                    (vpred_buf, "vpred_buf")):
+        if tuple(x.shape) != (b, t_len):
+            raise ValueError(f"rollout_record: {name} must be [{b}, {t_len}], got {tuple(x.shape)}")
+    if nan_flag.numel() != 1:
+        raise ValueError("rollout_record: nan_flag must hold one byte")
+    sb, sc = _chk_strided(act_buttons, torch.int64, b, "act_buttons"), _chk_strided(act_camera, torch.int64, b, "act_camera")
+    sl, sv = _chk_strided(log_prob, torch.float32, b, "log_prob"), _chk_strided(vpred, torch.float32, b, "vpred")
+    i64 = ctypes.c_int64
+    _call("vpt_rollout_record", dict(bytes=2.0 * b * frame_bytes), ptr(img), ptr(first8), ptr(act_buttons), ptr(act_camera), ptr(log_prob), ptr(vpred),
+          i64(sb), i64(sc), i64(sl), i64(sv), ptr(img_buf), ptr(fbuf8), ptr(act_buttons_buf), ptr(act_camera_buf), ptr(old_log_prob_buf), ptr(vpred_buf),
+          ptr(nan_flag), b, t_len, t, i64(frame_bytes), _stream())
+
+
+def rollout_reward(reward, done, t, reward_buf, done_return, done_length, ep_return, ep_length):
+    """The environment's answer to step t into column t, in place, one launch (vpt_rollout_reward).  reward fp32 [B]; done bool / uint8 [B]: the NEXT frame
+    starts an episode; reward_buf, done_return fp32 [B, T], done_length int32 [B, T]; ep_return fp32 [B], ep_length int32 [B]: the running totals of the
+    episodes in progress, advanced here and reset where done.  tests/rollout_ref.py is the float32 numpy twin (bit for bit)."""
+    _chk(reward, torch.float32, "reward"); _chk(reward_buf, torch.float32, "reward_buf"); _chk(done_return, torch.float32, "done_return")
+    _chk(done_length, torch.int32, "done_length"); _chk(ep_return, torch.float32, "ep_return"); _chk(ep_length, torch.int32, "ep_length")
+    if reward_buf.dim() != 2 or done_return.shape != reward_buf.shape or done_length.shape != reward_buf.shape:
+        raise ValueError(f"rollout_reward: reward_buf, done_return and done_length must share one [B, T] shape, got {tuple(reward_buf.shape)}, "
+                         f"{tuple(done_return.shape)}, {tuple(done_length.shape)}")
+    b, t_len = reward_buf.shape
+    t = int(t)
+    if not 0 <= t < t_len:
+        raise ValueError(f"rollout_reward: t = {t} is outside the horizon [0, {t_len})")
+    done8 = done.view(torch.uint8) if done.dtype == torch.bool else done
+    _chk(done8, torch.uint8, "done")
+    if reward.numel() != b or done8.numel() != b or ep_return.numel() != b or ep_length.numel() != b:
+        raise ValueError(f"rollout_reward: reward, done, ep_return and ep_length must hold {b} elements")
+    _call("vpt_rollout_reward", dict(bytes=22.0 * b), ptr(reward), ptr(done8), ptr(reward_buf), ptr(done_return), ptr(done_length), ptr(ep_return),
+          ptr(ep_length), b, t_len, t, _stream())
+
+
 def conv_backward_prepare(dy, y, res, stats_in, edge_sa, edge_sg, cin, dpooled=None, argmax=None, d_sa=None, d_sg=None, want_t12=False):
     """-> (dacc bf16 blocked, coef fp32 [F,2], d_sa fp32 [9,CoutPad], d_sg fp32 [9,CoutPad][, t12 double [F,2]]).
     coef = (c0, c1) of the statistics terms conv3x3_dgrad adds (dx += c0 + c1 x).  d_sa / d_sg are accumulated into when
