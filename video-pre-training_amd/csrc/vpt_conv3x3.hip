@@ -26,6 +26,16 @@
 //     VGPRs, no ds_write) into the double buffer one step ahead, so a step costs ONE barrier; the wait in front of the barrier is a
 //     counted s_waitcnt that retires the DMA only and leaves the younger halo / residual loads in flight.
 //   - The instruction order of a step is written out and pinned with sched_barrier (macros CONV_STEP / CONV_STEP16).
+// Halo DMA (template parameter HDMA: modes 0, 1, 4, 5 with 16-row tiles on an even count of 32-channel blocks -- what the launch function picks
+//   wherever it can; the plan above stays for every other case and is the bitwise reference of tests/test_gpu_conv_halo_dma.py):
+//   - LDS plan: [ring of four 8 KB one-tap weight slots 32 768][two dense, swizzled halo images of 324 pixels x 64 bytes 41 472][table, statistics,
+//     residual bias 5 184] = 79 424 bytes; the pool-fused mode's 69 632-byte output tile still fits below the table.
+//   - the halo of the NEXT channel block goes global -> LDS by buffer loads (21 pieces of 1 KB; out-of-image chunks carry an offset beyond the
+//     resource and arrive as zeros) into the image the current block does not read: no staging registers, no zero-fill selects, no ds_write and
+//     no second barrier per channel block.
+//   - K step = TWO taps (64 MFMAs per wave) of the global tap index t = 9 cb + 3 dy + dx, one barrier each; behind the barrier the pieces of taps
+//     t + 2 and t + 3 go into the slots of taps t - 2 and t - 1.  The loop body is two channel blocks; its vector-memory operations are counted.
+//   K order, accumulators, epilogue: unchanged, so every output bit is.  profiles/conv3x3_halo_dma.md has the measurements.
 // Forward modes (0, 1, 4, 5, 7): v_mfma_f32_16x16x32 main loop (8 pixel rows x 4 cout groups of 16x16 accumulators per wave), epilogue
 //   in the accumulators' own layout -- 16-byte loads and stores per lane, no lane exchange.  Halo records of odd pixels are shifted by
 //   16 bytes so that fragment reads and halo writes are bank-conflict-free (see FWD16 in the kernel).
@@ -50,7 +60,9 @@
 #endif
 // Timing-only ablations of the FORWARD main loop (wrong results; -DVPT_CONV_PROFILE builds only, chosen at compile time so that the unablated
 // loop carries no branch): -DVPT_CONV_FWD_ABLATE=1 no weight DMA inside the loop (stale weights), 2 no halo reloads (block 0's halo serves every
-// channel block), 4 both (MFMAs, fragment reads, waits and barriers only).  profiles/conv3x3_cycles.md has the table they gave.
+// channel block), 4 both (MFMAs, fragment reads, waits and barriers only).  profiles/conv3x3_cycles.md has the table they gave.  In the halo-DMA
+// instantiations the same switches drop the in-loop weight pieces (HWP: all four ring slots are filled once, in the prologue) and the in-loop halo
+// pieces (HXP: both images are filled once, with blocks 0 and 1); the counted waits then find fewer operations in flight and return at once.
 #if defined(VPT_CONV_PROFILE) && defined(VPT_CONV_FWD_ABLATE)
 #define FWD_NO_DMA (VPT_CONV_FWD_ABLATE == 1 || VPT_CONV_FWD_ABLATE == 4)
 #define FWD_NO_HALO (VPT_CONV_FWD_ABLATE == 2 || VPT_CONV_FWD_ABLATE == 4)
@@ -65,6 +77,11 @@
 #define KK_BYTES (9 * 128 * 4)          // 4608
 #define BT_OFF (KK_OFF + KK_BYTES + 64)  // 79744: per-channel residual bias of mode 5 (128 floats), after the block statistics' 64 bytes
 #define SMEM_BYTES (BT_OFF + 512)       // 80256: two workgroups per CU = 160512 of 163840 bytes
+// LDS plan of the halo-DMA instantiations (HDMA, see the kernel): [ring of four 8 KB tap slots][two dense halo images of 324 x 64 bytes][table ...]
+#define H_SLOT (128 * 64)               // one tap's weights: 128 couts x 32 cin
+#define H_RING (4 * H_SLOT)             // 32768
+#define H_BUF (324 * 64)                // 20736
+#define H_OOB 0x40000000u               // buffer offset of a halo chunk outside the image: beyond every resource, reads as zeros
 #define PT_RS 272                       // pixel pitch of the 16 x 16 x 128-channel output tile of the pool-fused mode (256 + 16 bytes)
 static_assert(256 * PT_RS <= KK_OFF, "the pooled mode's output tile must fit below the epilogue table");
 
@@ -99,16 +116,19 @@ template <int U> __device__ __forceinline__ void ac_set(f32x16& v, const f32x4 c
   else v = __builtin_shufflevector(v, w, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19);
 }
 
-template <bool TRACE, int MODE, int TR = 16>
+template <bool TRACE, int MODE, int TR = 16, bool HDMA = false>
 __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args a) {
   static_assert(TR == 16 || TR == 32, "tile rows");
+  static_assert(!HDMA || (TR == 16 && !TRACE && (MODE == 0 || MODE == 1 || MODE == 4 || MODE == 5)), "halo DMA: the 16-row forward modes but the arg-max one");
+  static_assert(!HDMA || 256 * PT_RS <= H_RING + 2 * H_BUF, "the pooled mode's output tile must fit below the epilogue table");
   constexpr int NWAVE = TR / 4, NTHR = 64 * NWAVE;
   constexpr int HPIX = (TR + 2) * 18;                            // halo pixels
   constexpr int NA = (HPIX * 4 + NTHR - 1) / NTHR;               // 16-byte halo chunks per thread and channel block: 6 / 5
   constexpr int NDMA = 24 / NWAVE;                               // 1 KB weight-DMA pieces per wave and step: 6 / 3
-  constexpr int A_SZ = HPIX * A_RS, KK_O = A_SZ + 2 * B_BYTES, BT_O = KK_O + KK_BYTES + 64, SMEM_SZ = BT_O + 512;
+  constexpr int A_SZ = HPIX * A_RS, KK_O = HDMA ? H_RING + 2 * H_BUF : A_SZ + 2 * B_BYTES, BT_O = KK_O + KK_BYTES + 64, SMEM_SZ = BT_O + 512;
   constexpr int NKK = (9 * 128 + NTHR - 1) / NTHR;
-  static_assert(TR != 16 || (A_SZ == A_BYTES && KK_O == KK_OFF && SMEM_SZ <= SMEM_BYTES), "16-row layout");
+  static_assert(TR != 16 || HDMA || (A_SZ == A_BYTES && KK_O == KK_OFF && SMEM_SZ <= SMEM_BYTES), "16-row layout");
+  static_assert(!HDMA || (SMEM_SZ == 79424 && 2 * SMEM_SZ <= 163840), "halo-DMA layout: two workgroups per CU");
   static_assert((MODE != 4 && MODE != 7) || TR == 16, "the pool-fused epilogue is written for 16 x 16 tiles");
   // 5 forward + residual through a per-frame affine:  out = relu(...) + res_scale[f] * res + res_bias[f][channel]  -- the block that
   // follows a stack's GroupNorm `n` reads the pooled tensor itself (already multiplied by n's gain) instead of a normalised copy
@@ -206,6 +226,38 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   // weight DMA: wave w moves pieces (NWAVE*m + w), m = 0..NDMA-1, of the 24 KB step tile; lane = 16-byte chunk
   const op16_t* wbase = a.wpk + (size_t)nt * NCB * 9 * 4096 + (size_t)(w * 64 + lane) * 8;
   unsigned char* bdst = smem + A_SZ + w * 1024;
+  // HDMA (forward modes 0, 1, 4, 5 on an even channel-block count): the halo is no longer register-staged.  Two DENSE halo images (64 bytes per
+  // pixel) are filled alternately by buffer loads to LDS -- no staging registers, no zero-fill selects, no ds_write, no second barrier -- and
+  // the weight double buffer is a ring of four one-tap slots.  Schedule: HSTEP below.
+  //   - image: the 16-byte slot 4 P + (q ^ ((hx >> 2) & 3)) holds chunk q of halo pixel P = 18 hy + hx.  The swizzle is a function of the
+  //     COLUMN only, so a fragment read is one of three per-lane bases (tap column dx) + an immediate (row, buffer).  A hardware
+  //     ds_read_b128 group reads 16 consecutive pixels of one halo row, chunk q of one pixel parity and q + 1 of the other: slot mod 16 =
+  //     4 (P & 3) + (q' ^ ((hx >> 2) & 3)); the four pixels of a class P & 3 share q' and are 4 columns apart, so (hx >> 2) & 3 separates
+  //     them -- 16 distinct slots for every tap offset.
+  //   - fill: 21 pieces of 1 KB (64 lanes x 16 bytes, destination contiguous, source per lane).  Wave w moves pieces 4 n + w, n = 0..4; the
+  //     last 1 KB of the image (n = 5: it overlaps piece 19, so no lane points beyond pixel 323) is written by every wave with the same data,
+  //     which keeps the number of vector-memory operations per wave fixed.  A chunk outside the image carries the offset H_OOB, beyond the
+  //     frame's resource: the range check delivers zeros (tests/test_gpu_conv_halo_dma.py: NaN surround).
+  unsigned hv[6] = {0u, 0u, 0u, 0u, 0u, 0u};       // per-lane source offset of the wave's six pieces inside one channel-block plane
+  if constexpr (HDMA) {
+#pragma unroll
+    for (int n = 0; n < 6; ++n) {
+      const int s = (n < 5 ? (4 * n + w) * 64 : (H_BUF - 1024) / 16) + lane;
+      const int P = s >> 2, hy = P / 18, hx = P - 18 * hy;
+      const int q = (s & 3) ^ ((hx >> 2) & 3);
+      const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;
+      hv[n] = (y >= 0 && y < a.H && x >= 0 && x < a.W) ? (unsigned)((y * a.W + x) * 64 + q * 16) : H_OOB;
+    }
+  }
+  // resources (scalar registers): this channel tile's packed weights, this frame's input planes -- exact sizes.  The *_n copies of the loop have
+  // num_records 0 in the last pass: what the schedule requests beyond the last channel block touches no memory and arrives as zeros.
+  const unsigned h_wbytes = (unsigned)NCB * 9u * (unsigned)H_SLOT, h_xbytes = (unsigned)NCB * (unsigned)HW * 64u;
+  const op16_t* const h_wptr = a.wpk + (size_t)nt * NCB * 9 * 4096;
+  const __amdgpu_buffer_rsrc_t hwrs = __builtin_amdgcn_make_buffer_rsrc((void*)h_wptr, 0, HDMA ? h_wbytes : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t hxrs = __builtin_amdgcn_make_buffer_rsrc((void*)xplane, 0, HDMA ? h_xbytes : 0u, 0x00020000);
+  const int h_wvoff = (w * 64 + lane) * 16;
+  unsigned char* const rdst = smem + w * 1024;     // ring slot s, piece 4 m + w: rdst + s * H_SLOT + m * 4096
+  int h_wso = 0, h_rpi = 0;                        // loop-carried: byte offset of the pass's first tap in the packed weights; 16384 in odd passes
 
   // ====================================================================================================================
   // Macros of BOTH main loops.  (All macros of the kernel are defined here, in three sections, and undefined together behind the epilogue
@@ -465,6 +517,48 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
       G16R(M16A, WB(0, 0, noff_), NOP_(), NEXT_DY, 0);                                                    \
     }                                                                                                     \
   } while (0)
+  // ---- HDMA schedule (modes 0, 1, 4, 5; even channel-block count).  K order unchanged: (channel block, kernel row, tap) -- every accumulator sees
+  // the MFMA sequence of CONV_STEP16.  One PASS of the loop = two channel blocks = local taps l = 0 .. 17 (block A: 0 .. 8 reads halo image 0,
+  // block B: 9 .. 17 image 1); tap l of pass i is global tap t = 18 i + l and lives in ring slot t & 3 = (l + 2 i) & 3: bases bWl* serve the taps
+  // with l & 2 == 0, bWh* the others, and both pairs swap slots {0, 1} <-> {2, 3} behind every pass.
+  // A STEP is two taps (2 k, 2 k + 1), 64 MFMAs per wave; its barrier sits in front of the LAST group of tap 2 k + 1, where every wave holds that
+  // group's fragments in registers and has finished taps 2 k - 1 and 2 k with all their LDS reads.  The counted wait in front of the barrier
+  // retires the weights of taps 2 k + 2 and 2 k + 3 (requested behind the previous barrier); behind it the pieces of taps 2 k + 4 and 2 k + 5 go
+  // into the slots of taps 2 k and 2 k + 1, one per group.  The groups' other slots carry the next block's halo: image 1 is requested behind the
+  // barrier of step 0 (the last reads of image 1 lie in front of the barrier of step 8 of the previous pass) and is counted home at the barrier of
+  // step 3, the last one before tap 8's refills read it; image 0 likewise behind the barrier of step 4, home at the barrier of step 8.  Modes 1 / 5
+  // request the residual's first row in step 7 of every pass (one instruction, always live; the last pass's value is the one the epilogue uses).
+  // Vector-memory operations per wave and pass, in order: see the X arguments of HSTEP in the loop; the n_late_ of a barrier counts those behind
+  // the step's last weight piece.
+#define HWP(lp_, m_, rs_)                                                                                 \
+  do { if (!FWD_NO_DMA) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (__attribute__((address_space(3))) void*)(rdst + ((((lp_) & 3) * H_SLOT) ^ h_rpi) + (m_) * 4096), \
+                                           16, h_wvoff, h_wso + (lp_) * H_SLOT + (m_) * 4096, 0, 0); } while (0)
+#define HXP_(n_, img_, rs_, cbo_)                                                                         \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_, (__attribute__((address_space(3))) void*)(smem + H_RING + (img_) * H_BUF + ((n_) < 5 ? w * 1024 + (n_) * 4096 : H_BUF - 1024)), \
+                                           16, hv[n_], cbo_, 0, 0)
+#define HXP(n_, img_, rs_, cbo_) do { if (!FWD_NO_HALO) HXP_(n_, img_, rs_, cbo_); } while (0)
+#define HPA(j_, l_) fp[j_] = *(const __attribute__((address_space(3))) op16x8*)(((l_) % 3 == 0 ? aH0 : ((l_) % 3 == 1 ? aH1 : aH2)) + (((l_) % 18) >= 9 ? H_BUF : 0) + ((j_) + ((l_) % 9) / 3) * (18 * 64))
+#define HWB(l_, u_) fw[(u_) & 1] = *(const __attribute__((address_space(3))) op16x8*)((((l_) & 2) ? (((u_) & 1) ? bWh1 : bWh0) : (((u_) & 1) ? bWl1 : bWl0)) + ((l_) & 1) * H_SLOT + ((u_) >> 1) * (32 * 64))
+#define HG(l_, u_, X) G16(M16A, u_, HWB(l_, (u_) + 1), X)
+#define HGR(l_, X)                                                                                        \
+  do {                                                                                                    \
+    M16A(0, 3); SB(); HWB((l_) + 1, 0); HPA(0, (l_) + 1); SB();                                           \
+    M16A(1, 3); SB(); HPA(1, (l_) + 1); SB();                                                             \
+    M16A(2, 3); SB(); HPA(2, (l_) + 1); SB();                                                             \
+    M16A(3, 3); SB(); HPA(3, (l_) + 1); X; SB();                                                          \
+    M16A(4, 3); SB(); HPA(4, (l_) + 1); SB();                                                             \
+    M16A(5, 3); SB(); HPA(5, (l_) + 1); SB();                                                             \
+    M16A(6, 3); SB(); HPA(6, (l_) + 1); SB();                                                             \
+    M16A(7, 3); SB(); HPA(7, (l_) + 1); SB();                                                             \
+  } while (0)
+  // step k_: X1 .. X3 = the weight pieces left of taps 2 k + 2, 2 k + 3; X4 .. X7 = halo / residual; WAITB; X0N = first piece of tap 2 k + 4
+#define HSTEP(k_, X1, X2, X3, X4, X5, X6, X7, WAITB, X0N)                                                 \
+  do {                                                                                                    \
+    HG(2 * (k_), 0, X1); HG(2 * (k_), 1, X2); HG(2 * (k_), 2, X3); HGR(2 * (k_), X4);                     \
+    HG(2 * (k_) + 1, 0, X5); HG(2 * (k_) + 1, 1, X6); HG(2 * (k_) + 1, 2, X7);                            \
+    WAITB;                                                                                                \
+    HGR(2 * (k_) + 1, X0N);                                                                               \
+  } while (0)
   // epilogue: edge class of pixel row j_ (only the wave's first / last row can touch the image border) and the constant-table prefetch
 #define EO16(j_) ((j_) == 0 ? eo_top : ((j_) == 7 ? eo_bot : 3 * 128))
 #define LOAD_KK16(c_)                                                                                     \
@@ -478,9 +572,20 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
   // ---- prologue: weights of step 0 (DMA), halo of channel block 0, epilogue constant table ----
+  if constexpr (HDMA) {   // taps 0 and 1 into ring slots 0 and 1, channel block 0 into halo image 0: retired by the __syncthreads() below
+    if (!FWD_NO_DMA) { HWP(0, 0, hwrs); HWP(0, 1, hwrs); HWP(1, 0, hwrs); HWP(1, 1, hwrs); }
+    else { for (int t_ = 0; t_ < 4; ++t_) { __builtin_amdgcn_raw_ptr_buffer_load_lds(hwrs, (__attribute__((address_space(3))) void*)(rdst + t_ * H_SLOT), 16, h_wvoff, t_ * H_SLOT, 0, 0);
+                                            __builtin_amdgcn_raw_ptr_buffer_load_lds(hwrs, (__attribute__((address_space(3))) void*)(rdst + t_ * H_SLOT + 4096), 16, h_wvoff, t_ * H_SLOT + 4096, 0, 0); } }
+    HXP_(0, 0, hxrs, 0); HXP_(1, 0, hxrs, 0); HXP_(2, 0, hxrs, 0); HXP_(3, 0, hxrs, 0); HXP_(4, 0, hxrs, 0); HXP_(5, 0, hxrs, 0);
+    if (FWD_NO_HALO) {   // (timing-only ablation: both images are filled once, here)
+      const unsigned cb1_ = (unsigned)HW * 64u;
+      HXP_(0, 1, hxrs, cb1_); HXP_(1, 1, hxrs, cb1_); HXP_(2, 1, hxrs, cb1_); HXP_(3, 1, hxrs, cb1_); HXP_(4, 1, hxrs, cb1_); HXP_(5, 1, hxrs, cb1_);
+    }
+  } else {
   ISSUE_B(0, 0);
 #pragma unroll
   for (int m = 0; m < NA; ++m) areg[m] = *(const u32x4*)((const char*)xplane + a_gbyte[m]);
+  }
   float mean = 0.f, rstd = 1.f, c0f = 0.f, c1f = 0.f;
   const float* esa = a.edge_sa;
   if (!BWD) {
@@ -526,7 +631,9 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
     res_s = a.res_scale[f];
     if (tid < 128) ((float*)(smem + BT_O))[tid] = (nt * 128 + tid < a.Cout) ? a.res_bias[(size_t)f * a.Cout + nt * 128 + tid] : 0.f;
   }
-  if constexpr (FWD16) {
+  if constexpr (HDMA) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the prologue's pieces are home before the barrier, whatever the fence below waits for
+  } else if constexpr (FWD16) {
 #pragma unroll
     for (int m = 0; m < NA; ++m) HALO_WR16(m);
   } else {
@@ -557,7 +664,16 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   // cout group u = 2 blk + b: row 32 blk + 8 (c16 >> 2) + 4 b + (c16 & 3), swizzle ((row >> 2) & 3) = (2 (c16 >> 2) + b) & 3
   lds_cptr bW0 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2)) & 3)) << 4);
   lds_cptr bW1 = (lds_cptr)smem + A_SZ + (wn * 64 + 8 * (c16 >> 2) + 4 + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2) + 1) & 3)) << 4);
-  if constexpr (FWD16) { asm volatile("" : "+v"(aLe), "+v"(aLo), "+v"(bW0), "+v"(bW1)); }
+  if constexpr (FWD16 && !HDMA) { asm volatile("" : "+v"(aLe), "+v"(aLo), "+v"(bW0), "+v"(bW1)); }
+  // HDMA fragment bases: one per tap column dx (the image's swizzle is a function of the halo column pcol + dx), the weight rows in ring slot 0 / 2
+#define HA_BASE(dx_) ((lds_cptr)smem + H_RING + ((wm * 8) * 18 + pcol + (dx_)) * 64 + ((q16 ^ (((pcol + (dx_)) >> 2) & 3)) << 4))
+  lds_cptr aH0 = HA_BASE(0), aH1 = HA_BASE(1), aH2 = HA_BASE(2);
+#undef HA_BASE
+  lds_cptr bWl0 = (lds_cptr)smem + (wn * 64 + 8 * (c16 >> 2) + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2)) & 3)) << 4);
+  lds_cptr bWl1 = (lds_cptr)smem + (wn * 64 + 8 * (c16 >> 2) + 4 + (c16 & 3)) * 64 + ((q16 ^ ((2 * (c16 >> 2) + 1) & 3)) << 4);
+  lds_cptr bWh0 = bWl0 + 2 * H_SLOT, bWh1 = bWl1 + 2 * H_SLOT;
+  int h_swap = 2 * H_SLOT;
+  if constexpr (HDMA) { asm volatile("" : "+v"(aH0), "+v"(aH1), "+v"(aH2), "+v"(bWl0), "+v"(bWl1), "+v"(bWh0), "+v"(bWh1)); }
 
   // epilogue addressing (needed early: the residual is requested during the last channel block)
   // Dgrad epilogue: operands are SWAPPED in the MFMA (weights = A rows, pixels = B columns): a lane holds ONE pixel (column l31 of the
@@ -602,7 +718,47 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
   const int wvoff = (w * 64 + lane) * 16;
 
   if (TRACE && (FWD16 || tid == 0)) t_trace[1] = wall_clock64();
-  if constexpr (FWD16) {
+  if constexpr (HDMA) {
+    if (CONV_ABLATE != 2) {
+      HWP(2, 0, hwrs);          // (the piece the last group of a pass requests for the next one)
+      HWB(0, 0);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) HPA(j, 0);
+      SB();
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ac[j] = zero16;
+      const int NPASS = NCB >> 1;
+#pragma unroll 1
+      for (int ps = 0; ps < NPASS; ++ps) {
+        const bool more = ps + 1 < NPASS;
+        const __amdgpu_buffer_rsrc_t hwrs_n = __builtin_amdgcn_make_buffer_rsrc((void*)h_wptr, 0, more ? h_wbytes : 0u, 0x00020000);
+        const __amdgpu_buffer_rsrc_t hxrs_n = __builtin_amdgcn_make_buffer_rsrc((void*)xplane, 0, more ? h_xbytes : 0u, 0x00020000);
+        const unsigned cbB = (unsigned)(2 * ps + 1) * (unsigned)HW * 64u, cbA = cbB + (unsigned)HW * 64u;   // bytes; uniform
+        HSTEP(0, HWP(2, 1, hwrs), HWP(3, 0, hwrs), HWP(3, 1, hwrs), NOP_(), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(0), HWP(4, 0, hwrs));
+        HSTEP(1, HWP(4, 1, hwrs), HWP(5, 0, hwrs), HWP(5, 1, hwrs), HXP(0, 1, hxrs, cbB), HXP(1, 1, hxrs, cbB), HXP(2, 1, hxrs, cbB), HXP(3, 1, hxrs, cbB), WAIT_BARRIER(4), HWP(6, 0, hwrs));
+        HSTEP(2, HWP(6, 1, hwrs), HWP(7, 0, hwrs), HWP(7, 1, hwrs), HXP(4, 1, hxrs, cbB), HXP(5, 1, hxrs, cbB), NOP_(), NOP_(), WAIT_BARRIER(2), HWP(8, 0, hwrs));
+        HSTEP(3, HWP(8, 1, hwrs), HWP(9, 0, hwrs), HWP(9, 1, hwrs), NOP_(), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(0), HWP(10, 0, hwrs));
+        HSTEP(4, HWP(10, 1, hwrs), HWP(11, 0, hwrs), HWP(11, 1, hwrs), NOP_(), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(0), HWP(12, 0, hwrs));
+        HSTEP(5, HWP(12, 1, hwrs), HWP(13, 0, hwrs), HWP(13, 1, hwrs), HXP(0, 0, hxrs_n, cbA), HXP(1, 0, hxrs_n, cbA), HXP(2, 0, hxrs_n, cbA), HXP(3, 0, hxrs_n, cbA), WAIT_BARRIER(4), HWP(14, 0, hwrs));
+        HSTEP(6, HWP(14, 1, hwrs), HWP(15, 0, hwrs), HWP(15, 1, hwrs), HXP(4, 0, hxrs_n, cbA), HXP(5, 0, hxrs_n, cbA), NOP_(), NOP_(), WAIT_BARRIER(2), HWP(16, 0, hwrs));
+        if constexpr (HAS_RES) {   // compile-time: without a residual the loads would be dead code and the count wrong
+          HSTEP(7, HWP(16, 1, hwrs), HWP(17, 0, hwrs), HWP(17, 1, hwrs), XR16(0), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(2), HWP(18, 0, hwrs_n));
+        } else {
+          HSTEP(7, HWP(16, 1, hwrs), HWP(17, 0, hwrs), HWP(17, 1, hwrs), NOP_(), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(0), HWP(18, 0, hwrs_n));
+        }
+        HSTEP(8, HWP(18, 1, hwrs_n), HWP(19, 0, hwrs_n), HWP(19, 1, hwrs_n), NOP_(), NOP_(), NOP_(), NOP_(), WAIT_BARRIER(0), HWP(20, 0, hwrs_n));
+        h_wso += 18 * H_SLOT;
+        h_rpi ^= 2 * H_SLOT;
+        bWl0 += h_swap; bWl1 += h_swap; bWh0 -= h_swap; bWh1 -= h_swap;
+        h_swap = -h_swap;
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the (empty) pieces of the last pass are retired before the workgroup's LDS is given up
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ac[j] = zero16;
+      __syncthreads();
+    }
+  } else if constexpr (FWD16) {
     if (CONV_ABLATE != 2) {
       WB(0, 0, 0);
 #pragma unroll
@@ -1091,6 +1247,14 @@ __global__ __launch_bounds__(TR * 16, 2) void vpt_conv3x3_kernel(VptConv3x3Args 
 #undef XR16
 #undef XR16L
 #undef CONV_STEP16
+#undef HWP
+#undef HXP_
+#undef HXP
+#undef HPA
+#undef HWB
+#undef HG
+#undef HGR
+#undef HSTEP
 #undef EO16
 #undef LOAD_KK16
   float s_sum = s_sum2.x + s_sum2.y, s_sq = s_sq2.x + s_sq2.y;
@@ -1322,6 +1486,12 @@ __global__ __launch_bounds__(512, 1) void vpt_conv3x3_small_kernel(VptConv3x3Arg
 static long long* g_conv_trace = nullptr;
 extern "C" void vpt_conv3x3_set_trace(void* buf) { g_conv_trace = (long long*)buf; }  // profiling: [grid][12] int64, or null
 
+// which forward modes take the halo-DMA instantiation where the shape allows it: bit 0 = modes 0, 1, 5; bit 1 = the pool-fused mode 4
+#define HALO_DMA_DEFAULT 3
+static int g_conv_halo_dma = HALO_DMA_DEFAULT;
+// tests and A/B measurements: 0 = the register-staged path everywhere, a negative value = the shipped selection; returns the previous mask
+extern "C" int vpt_conv3x3_set_halo_dma(int mask) { const int was = g_conv_halo_dma; g_conv_halo_dma = mask < 0 ? HALO_DMA_DEFAULT : (mask & 3); return was; }
+
 extern "C" int vpt_conv3x3_launch(const VptConv3x3Args* a_in, hipStream_t stream) {
   int ablate = 0, extra_lds = 0;
 #ifdef VPT_CONV_PROFILE
@@ -1364,6 +1534,13 @@ extern "C" int vpt_conv3x3_launch(const VptConv3x3Args* a_in, hipStream_t stream
 #define LAUNCH_(T_, M_) hipLaunchKernelGGL((vpt_conv3x3_kernel<T_, M_>), dim3((unsigned)grid), dim3(256), extra_lds, stream, *a)
   if (a->trace && mode > 3) return -1;
   if (mode == 6) { LAUNCH_(false, 6); return hipGetLastError() == hipSuccess ? 0 : -3; }
+  // Halo DMA (HDMA): the 16-row forward modes on an even count of 32-channel blocks (a pass of its loop is two blocks) whose frame fits the
+  // 2^30-byte offset range below H_OOB.  Everything else -- odd counts, tracing, profile builds with extra LDS -- runs the register-staged
+  // instantiation, which is also the bitwise reference of tests/test_gpu_conv_halo_dma.py (vpt_conv3x3_set_halo_dma(0) sends every launch there).
+  const bool hdma_shape = !a->bwd && !a->trace && !extra_lds && ((a->Cin >> 5) & 1) == 0 && (long long)(a->Cin >> 5) * a->H * a->W * 64 < (long long)H_OOB;
+#define LAUNCHH_(M_) hipLaunchKernelGGL((vpt_conv3x3_kernel<false, M_, 16, true>), dim3((unsigned)grid), dim3(256), 0, stream, *a)
+  // (mode 7, the pool-fused training forward with arg-max masks, lost 4 % on the K = 1152 layer under the new schedule and won 2.5 % on the K = 2304
+  // one -- profiles/conv3x3_halo_dma.md -- so it keeps the register-staged instantiation)
   if (mode == 7) { LAUNCH_(false, 7); return hipGetLastError() == hipSuccess ? 0 : -3; }
   // tiling 3 (forward) = the 32-row, eight-wave tiles wherever the image has whole 32-row bands.  Measured at parity with the 16-row tiles on
   // every layer shape (profiles/r04_experiments.md section 7: halving the weight DMA buys nothing on a power-limited chip), so the shipped
@@ -1375,6 +1552,11 @@ extern "C" int vpt_conv3x3_launch(const VptConv3x3Args* a_in, hipStream_t stream
 #undef LAUNCH32_
     return hipGetLastError() == hipSuccess ? 0 : -3;
   }
+  if (hdma_shape && (((g_conv_halo_dma & 1) && (mode == 0 || mode == 1 || mode == 5)) || ((g_conv_halo_dma & 2) && mode == 4))) {
+    if (mode == 0) LAUNCHH_(0); else if (mode == 1) LAUNCHH_(1); else if (mode == 4) LAUNCHH_(4); else LAUNCHH_(5);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+  }
+#undef LAUNCHH_
   if (a->trace) { if (mode == 0) LAUNCH_(true, 0); else if (mode == 1) LAUNCH_(true, 1); else if (mode == 2) LAUNCH_(true, 2); else LAUNCH_(true, 3); }
   else { if (mode == 0) LAUNCH_(false, 0); else if (mode == 1) LAUNCH_(false, 1); else if (mode == 2) LAUNCH_(false, 2); else if (mode == 3) LAUNCH_(false, 3); else if (mode == 4) LAUNCH_(false, 4); else LAUNCH_(false, 5); }
 #undef LAUNCH_
