@@ -1,5 +1,5 @@
 """The kernels behind the CNN gradients -- vpt_conv_bwd_prep_kernel (dy, dy + res, arg-max bytes), vpt_conv_bwd_prep_pooled_kernel,
-vpt_conv_backward_reduce, vpt_conv3x3_kernel modes 2 / 3 / 6 and vpt_conv_wgrad_kernel<16|32|64> with its reduce -- held per element to the
+vpt_conv_backward_reduce, vpt_conv3x3_dgrad_kernel modes 2 / 3 / 6 and vpt_conv_wgrad_kernel<16|32|64> with its reduce -- held per element to the
 fp64 reference of tests/cnn_backward_ref.py on the SAME stored 16-bit tensors, in both operand formats.  Needs an MI355X.
 
 The forward runs once per case on the GPU (ops.conv3x3) so that the stored output has realistic gates; every backward op and the reference
@@ -165,7 +165,7 @@ def _dgrad_reference(name, fmt):
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 @pytest.mark.parametrize("name", list(CASES))
 def test_dgrad_fp64(name, fmt, use_skip):
-    """vpt_conv3x3_kernel modes 2 (no skip) and 3 (skip) on the reference's operand rounded to 16 bits."""
+    """vpt_conv3x3_dgrad_kernel modes 2 (no skip) and 3 (skip) on the reference's operand rounded to 16 bits."""
     c = _case(name, fmt)
     dacc16, coef, dx0, conv_abs = _dgrad_reference(name, fmt)
     dx = ops.conv3x3_dgrad(_blocked(dacc16, c["dt"]), c["wt"], c["cin"], skip=c["skipb"] if use_skip else None, xin=c["xb"], coef=coef.to(DEV))
@@ -203,7 +203,7 @@ def _block(name, fmt):
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 @pytest.mark.parametrize("name", BLOCK_CASES)
 def test_gated_dgrad_and_reduce_fp64(name, fmt):
-    """vpt_conv3x3_kernel mode 6 (conv0's operand rstd0 (conv^T + c0 + c1 xin) [xin > 0] and gate_u) and, on the operand it stored,
+    """vpt_conv3x3_dgrad_kernel mode 6 (conv0's operand rstd0 (conv^T + c0 + c1 xin) [xin > 0] and gate_u) and, on the operand it stored,
     vpt_conv_bwd_prep_kernel<pre-gated> = ops.conv_backward_reduce."""
     b = _block(name, fmt)
     ch, h, w = b["cin"], b["h"], b["w"]

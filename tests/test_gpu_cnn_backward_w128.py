@@ -191,7 +191,7 @@ def test_wgrad_w128(name, fmt, prefill):
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
 @pytest.mark.parametrize("name", list(CASES))
 def test_dgrad_w128(name, fmt, use_skip):
-    """vpt_conv3x3_kernel modes 2 / 3 at W = 128 (the IDM's dx0, the gradient the temporal conv's backward reads)."""
+    """vpt_conv3x3_dgrad_kernel modes 2 / 3 at W = 128 (the IDM's dx0, the gradient the temporal conv's backward reads)."""
     c = _case(name, fmt)
     r = _pooled_reference(name, fmt)
     dacc16, coef = r.dacc.to(c["dt"]), r.coef.float()

@@ -1,10 +1,10 @@
-"""Record the expected hashes of tests/test_gpu_conv_fwd_bitwise.py from a pair of REFERENCE libraries (the parent commit's builds of
-libvpt_hip.so and libvpt_hip_f16.so, e.g. copied aside before the kernel is changed, or made by tools/build_ref_lib.sh):
+"""Record the expected hashes of tests/test_gpu_conv_fwd_bitwise.py and tests/test_gpu_conv_dgrad_bitwise.py from a pair of REFERENCE libraries
+(the parent commit's builds of libvpt_hip.so and libvpt_hip_f16.so, e.g. copied aside before the kernel is changed, or made by tools/build_ref_lib.sh):
 
-    python tools/conv_hash_record.py <reference bf16 .so> <reference fp16 .so> [out.json]
+    python tools/conv_hash_record.py <reference bf16 .so> <reference fp16 .so> [forward out.json [dgrad out.json]]
 
-Writes {format: {case: {mode tag: sha256}}} (default: tests/golden/conv3x3_fwd_hashes.json); the test then holds the working tree's libraries
-to those bits.  Every case is computed twice and must hash the same both times.  Needs an MI355X."""
+Writes {format: {case: {mode tag: sha256}}} per test (default: tests/golden/conv3x3_fwd_hashes.json, tests/golden/conv3x3_dgrad_hashes.json); the
+tests then hold the working tree's libraries to those bits.  Every case is computed twice and must hash the same both times.  Needs an MI355X."""
 import json
 import os
 import sys
@@ -19,17 +19,16 @@ from vpt_amd import _native  # noqa: E402
 
 _native._LIB_PATHS["fp16"] = os.path.abspath(sys.argv[2])
 assert not _native._libs, "a library was loaded before the reference paths were set"
+from tests import test_gpu_conv_dgrad_bitwise as TD  # noqa: E402
 from tests import test_gpu_conv_fwd_bitwise as T  # noqa: E402
 
 
-def main():
-    path = sys.argv[3] if len(sys.argv) > 3 else T.GOLDEN
-    print("reference libraries:", _native._LIB_PATHS)
+def record(mod, path):
     out = {}
     for fmt in ("bf16", "fp16"):
         out[fmt] = {}
-        for name in T.CASES:
-            a, b = T.case_hashes(name, fmt), T.case_hashes(name, fmt)
+        for name in mod.CASES:
+            a, b = mod.case_hashes(name, fmt), mod.case_hashes(name, fmt)
             if a != b:
                 raise SystemExit(f"{name} {fmt}: two runs of the same library disagree: {[k for k in a if a[k] != b[k]]}")
             out[fmt][name] = a
@@ -39,6 +38,12 @@ def main():
         json.dump(out, f, indent=1, sort_keys=True)
         f.write("\n")
     print("wrote", path)
+
+
+def main():
+    print("reference libraries:", _native._LIB_PATHS)
+    record(T, sys.argv[3] if len(sys.argv) > 3 else T.GOLDEN)
+    record(TD, sys.argv[4] if len(sys.argv) > 4 else TD.GOLDEN)
 
 
 if __name__ == "__main__":

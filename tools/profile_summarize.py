@@ -34,10 +34,11 @@ for sub, name in (("fwd1", "fwd_singlestream"), ("fwd1_fp16", "fwd_singlestream_
     if line:
         open(os.path.join(DST, f"{TAG}_bench_{name}_under_rocprof.json"), "w").write(line + "\n")
     if f:
-        rows = [r for r in csv.DictReader(open(f)) if "vpt_conv3x3_kernel" in r["Name"]]
+        # all conv3x3 launches: the forward kernel and (the BC leg) the dgrad kernel
+        rows = [r for r in csv.DictReader(open(f)) if "vpt_conv3x3_kernel" in r["Name"] or "vpt_conv3x3_dgrad_kernel" in r["Name"]]
         tot = sum(float(r["TotalDurationNs"]) for r in rows)
         n = sum(int(r["Calls"]) for r in rows)
-        print(f"{sub}: vpt_conv3x3_kernel {n} launches, {tot / 1e6:.1f} ms total, {tot / max(n, 1) / 1e3:.1f} us average")
+        print(f"{sub}: vpt_conv3x3_kernel + vpt_conv3x3_dgrad_kernel {n} launches, {tot / 1e6:.1f} ms total, {tot / max(n, 1) / 1e3:.1f} us average")
 
 # (2b) single-stream BC step (round 5)
 f = one("bc1/**/*_kernel_stats.csv")

@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["vpt_conv3x3.hip", "vpt_conv_first.hip", "vpt_conv3d.hip", "vpt_elementwise.hip", "vpt_gemm.hip", "vpt_gemv.hip", "vpt_action_codec.hip", "vpt_labeler.hip", "vpt_clip.hip", "vpt_augment.hip",
+SOURCES = ["vpt_conv3x3.hip", "vpt_conv3x3_fwd.hip", "vpt_conv3x3_dgrad.hip", "vpt_conv3x3_small.hip", "vpt_conv_first.hip", "vpt_conv3d.hip", "vpt_elementwise.hip", "vpt_gemm.hip", "vpt_gemv.hip", "vpt_action_codec.hip", "vpt_labeler.hip", "vpt_clip.hip", "vpt_augment.hip",
            "vpt_transformer.hip", "vpt_optim.hip", "vpt_grad_norm.hip", "vpt_backward.hip", "vpt_cnn_backward.hip", "vpt_conv_wgrad.hip", "vpt_conv_first_bwd.hip", "vpt_pack.hip", "vpt_reduce.hip", "vpt_rl.hip", "vpt_ppg.hip", "vpt_rollout.hip", "vpt_capi.hip"]
 LIB = os.path.join(HERE, "libvpt_hip.so")
 LIB_F16 = os.path.join(HERE, "libvpt_hip_f16.so")   # same sources, 16-bit operands = IEEE half (precision="fp16")
@@ -31,7 +31,7 @@ REMARKS = ["-Rpass-analysis=kernel-resource-usage"]
 EXTRA_FLAGS = {"vpt_backward.hip": ["-fno-slp-vectorize"], "vpt_rl.hip": ["-fno-slp-vectorize"], "vpt_ppg.hip": ["-fno-slp-vectorize"], "vpt_conv3d.hip": ["-fno-slp-vectorize"], "vpt_conv_first.hip": ["-fno-slp-vectorize"],
                "vpt_grad_norm.hip": ["-fno-slp-vectorize"], "vpt_augment.hip": ["-fno-slp-vectorize"]}      # vpt_augment.hip: the compiler forms such adds in the bilinear sums without it
 VARIANTS = [(LIB, "bf16", []), (LIB_F16, "f16", ["-DVPT_OPERAND_F16"])]
-# Test-only A/B library (never loaded by the product: tests/test_gpu_conv_clamp.py names it through VPT_HIP_LIB): the bf16 library with vpt_conv3x3.hip's
+# Test-only A/B library (never loaded by the product: tests/test_gpu_conv_clamp.py names it through VPT_HIP_LIB): the bf16 library with vpt_conv3x3_fwd.hip's
 # residual epilogues built WITHOUT the inline-assembly clamp FMA (the fp32 v_max ReLU of rounds 1-4) -- the two must agree bit for bit.
 LIB_NOCLAMP = os.path.join(HERE, "build", "libvpt_noclamp.so")
 
@@ -112,9 +112,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(f"built {lib} ({os.path.getsize(lib) // 1024} KiB)")
     objdir = os.path.join(HERE, "build", "var_noclamp")
     os.makedirs(objdir, exist_ok=True)
-    obj = os.path.join(objdir, "vpt_conv3x3.o")
-    subprocess.check_call([hipcc] + FLAGS + ["-DVPT_EPI_NO_CLAMP_RELU=1", "-c", os.path.join(CSRC, "vpt_conv3x3.hip"), "-o", obj], stderr=subprocess.DEVNULL)
-    others = [o for o in link[0][1] if not o.endswith("vpt_conv3x3.o")]
+    obj = os.path.join(objdir, "vpt_conv3x3_fwd.o")      # (the clamp is a matter of the forward epilogue: the other objects are the bf16 build's)
+    subprocess.check_call([hipcc] + FLAGS + ["-DVPT_EPI_NO_CLAMP_RELU=1", "-c", os.path.join(CSRC, "vpt_conv3x3_fwd.hip"), "-o", obj], stderr=subprocess.DEVNULL)
+    others = [o for o in link[0][1] if not o.endswith("vpt_conv3x3_fwd.o")]
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_NOCLAMP] + others + [obj])
     with open(stamp, "w") as f:
         f.write(fp)

@@ -367,7 +367,7 @@ struct PrepRow {
   uint64_t am[4];
 };
 
-// PRE (round 5): `dy` is the operand dacc = rstd dz ITSELF, written by the producing dgrad's epilogue (vpt_conv3x3_kernel mode 6: a block's
+// PRE (round 5): `dy` is the operand dacc = rstd dz ITSELF, written by the producing dgrad's epilogue (vpt_conv3x3_dgrad_kernel mode 6: a block's
 // conv1 -> conv0, no residual): one tensor read, nothing written; the sums are those of dacc, scaled back by 1 / rstd when they are
 // stored, and the data term sum dz v arrives per frame (gate_u).
 template <bool HAS_DY, bool HAS_RES, bool PRE = false>

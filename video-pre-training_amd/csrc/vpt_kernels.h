@@ -261,7 +261,7 @@ struct VptConvBwdPrepArgs {
   float* d_sg;
   int frames, CB, H, W, CoutPad;
   double inv_count_in;     // 1 / (Cin*H*W)
-  // pre-gated variant (round 5): `dy` IS the operand dacc = rstd dz already (written by the gated dgrad, vpt_conv3x3_kernel mode 6); y, res and
+  // pre-gated variant (round 5): `dy` IS the operand dacc = rstd dz already (written by the gated dgrad, vpt_conv3x3_dgrad_kernel mode 6); y, res and
   // dacc are unused, nothing is written but the per-frame sums: S[e][o] = (sum dacc) / rstd, and the data term sum dz v = gate_u[f] / rstd
   const double* gate_u;
   // pooled variant (round 5; dy, y, res, argmax unused): the layer feeds the max-pool and was run pool-fused with arg-max masks (vpt_conv3x3_kernel
@@ -591,6 +591,11 @@ long vpt_colsum_partial_floats(int M, int N);
 long vpt_slab_sum_scratch_floats(int rows, int cols);
 int vpt_slab_sum_launch(const float* slab, int rows, int cols, long ld, float* out_a, int split, float* out_b, int accumulate, float* scratch, hipStream_t s);
 int vpt_conv3x3_launch(const VptConv3x3Args* a, hipStream_t s);
+// internal launchers of vpt_conv3x3_launch, one per kernel family (a kernel is launched from the translation unit that defines it): validated
+// arguments plus what the launch function decided; they launch and report nothing (the caller reads hipGetLastError)
+void vpt_conv3x3_fwd_launch(const VptConv3x3Args* a, int mode, int variant, long grid, int extra_lds, hipStream_t s);   // vpt_conv3x3_fwd.hip
+void vpt_conv3x3_dgrad_launch(const VptConv3x3Args* a, int mode, long grid, int extra_lds, hipStream_t s);              // vpt_conv3x3_dgrad.hip
+void vpt_conv3x3_small_launch(const VptConv3x3Args* a, long grid, hipStream_t s);                                       // vpt_conv3x3_small.hip
 int vpt_pool_seam_launch(const VptPoolSeamArgs* a, hipStream_t s);
 int vpt_channel_stats_launch(const VptChannelStatsArgs* a, hipStream_t s);
 int vpt_nfold_coef_launch(const VptNfoldCoefArgs* a, hipStream_t s);
