@@ -384,6 +384,18 @@ int vpt_adam_step_multi_clip(const void* table, int ntensors, int64_t total_bloc
                              float eps, float weight_decay, float grad_scale, const int32_t* skip_flag, const float* clip_coef,
                              void* stream);
 
+/* Parameter groups (th.optim.Adam([dict(params=..., lr=..., weight_decay=...), ...]), the list form of the optimiser
+ * behavioural_cloning.py:63-67 builds with one group) and decoupled decay, still ONE launch over the SAME table as vpt_adam_step_multi.
+ * `groups` is a DEVICE array of `ntensors` records { float lr; float weight_decay; } (8 bytes each), record i belonging to table
+ * entry i.  Coupled (decoupled == 0): per element the arithmetic of vpt_adam_step_multi[_clip] with the tensor's own lr and
+ * weight_decay; the step size is (float)((double)lr / (1 - pow((double)beta1, step))), the same double expression on the float lr,
+ * so a tensor whose record holds vpt_adam_step_multi's launch-wide values is updated bit for bit as by that entry point.
+ * decoupled != 0 (th.optim.AdamW): param = param * (float)(1 - (double)lr * (double)weight_decay) first -- the factor formed in
+ * double and rounded to float, one rounded multiply --, then the coupled update with weight_decay = 0.
+ * skip_flag: as vpt_adam_step_multi.  clip_coef (optional device scalar): as vpt_adam_step_multi_clip; null = unclipped. */
+int vpt_adam_step_groups(const void* table, const void* groups, int ntensors, int64_t total_blocks, int step, float beta1, float beta2,
+                         float eps, float grad_scale, int decoupled, const int32_t* skip_flag, const float* clip_coef, void* stream);
+
 /* Gradient accumulation over micro-batches: param[i] = param[i] + grad[i] (one fp32 add) for every tensor of the SAME table as
  * vpt_adam_step_multi, in one launch.  `param` names the fp32 accumulator (read and written), `grad` the addend (read only);
  * exp_avg and exp_avg_sq are ignored.  No reductions and no atomics -- the same inputs give the same bits -- and no byte outside

@@ -89,6 +89,7 @@ SIGNATURES = {
     "vpt_grad_norm_multi": [_P, _I, _L, _F, _F, _P, _P, _P, _P, _P],
     "vpt_adam_step_multi_clip": [_P, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P],
     "vpt_grad_accumulate_multi": [_P, _I, _L, _P],
+    "vpt_adam_step_groups": [_P, _P, _I, _L, _I, _F, _F, _F, _F, _I, _P, _P, _P],
     "vpt_layernorm_linear_forward": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vpt_masked_attention_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vpt_masked_attention_step_inplace": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

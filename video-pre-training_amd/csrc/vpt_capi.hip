@@ -551,6 +551,21 @@ int vpt_adam_step_multi_clip(const void* table, int ntensors, int64_t total_bloc
   return adam_step_multi_impl("vpt_adam_step_multi_clip", table, ntensors, total_blocks, step, lr, beta1, beta2, eps, weight_decay, grad_scale, skip_flag, clip_coef, stream);
 }
 
+int vpt_adam_step_groups(const void* table, const void* groups, int ntensors, int64_t total_blocks, int step, float beta1, float beta2, float eps,
+                         float grad_scale, int decoupled, const int32_t* skip_flag, const float* clip_coef, void* stream) {
+  if (step < 1) return fail(-1, "vpt_adam_step_groups: step counts from 1");
+  if ((!table || !groups) && ntensors > 0) return fail(-1, "vpt_adam_step_groups: null table / groups");
+  if (ntensors < 0 || total_blocks < 0) return fail(-1, "vpt_adam_step_groups: negative tensor / block count");
+  VptAdamArgs a = {};
+  a.p = nullptr; a.g = nullptr; a.m = nullptr; a.v = nullptr; a.n = 0; a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = 0.0f; a.grad_scale = grad_scale;
+  a.step_size = 0.0f;      // per tensor: (float)((double)lr / bias_correction1), formed in the kernel
+  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  const double bias_correction1 = 1.0 - pow((double)beta1, (double)step);
+  CHECK_LAUNCH(vpt_adam_groups_launch((const VptAdamTensor*)table, (const VptAdamGroup*)groups, ntensors, (long)total_blocks, &a, bias_correction1,
+                                      decoupled != 0, (hipStream_t)stream), "vpt_adam_step_groups");
+}
+
 long vpt_grad_norm_workspace_bytes(int ntensors, int64_t total_blocks) {
   const long f = vpt_grad_norm_workspace_floats(ntensors, (long)total_blocks);
   return f < 0 ? -1 : 4 * f;

@@ -516,6 +516,11 @@ struct VptAdamTensor {      // one parameter tensor of a multi-tensor Adam step 
   long long first_block;    // first 1024-element block of the launch that belongs to this tensor
 };
 
+struct VptAdamGroup {       // the hyper-parameters of one tensor of vpt_adam_groups_launch (device array parallel to the VptAdamTensor table)
+  float lr;
+  float weight_decay;
+};
+
 struct VptAdamArgs {
   float* p;                // parameters (updated in place)
   const float* g;          // gradients
@@ -537,6 +542,8 @@ int vpt_pack_conv3d_t5_launch(const float* w, const float* bias, void* out, floa
 int vpt_chw_to_blocked_launch(const float* src, float* dst, long rows, int C, int H, int W, hipStream_t s);
 int vpt_adam_launch(const VptAdamArgs* a, hipStream_t s);
 int vpt_adam_multi_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, const VptAdamArgs* h, hipStream_t s);
+int vpt_adam_groups_launch(const VptAdamTensor* table_dev, const VptAdamGroup* groups_dev, int ntensors, long total_blocks, const VptAdamArgs* h,
+                           double bias_correction1, int decoupled, hipStream_t s);
 int vpt_grads_nonfinite_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, int* flag, hipStream_t s);
 long vpt_grad_norm_workspace_floats(int ntensors, long total_blocks);
 int vpt_grad_norm_launch(const VptAdamTensor* table_dev, int ntensors, long total_blocks, float grad_scale, float max_norm, float* workspace,

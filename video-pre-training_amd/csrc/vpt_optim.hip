@@ -100,6 +100,74 @@ extern "C" int vpt_adam_multi_launch(const VptAdamTensor* table_dev, int ntensor
 }
 
 
+// ---- parameter groups: the multi-tensor launch with ONE {lr, weight_decay} PER TENSOR (torch.optim.Adam(param_groups), the list form of
+// behavioural_cloning.py:63-67) and, with DECOUPLED, torch.optim.AdamW's decay.  Same table, same block mapping, same 28 B/parameter; `groups` is a
+// device array parallel to the table, read at the index the binary search found (per TENSOR, never per block).
+// Coupled: the expression sequence of vpt_adam_multi_kernel with weight_decay and step_size taken from the tensor's record; the step size is that
+// entry point's own double expression (float)((double)lr / (1 - beta1^t)) on the float lr -- one fp64 division per thread on the launch-wide
+// bias_correction1 = 1 - pow((double)beta1, t) -- so a tensor whose (lr, wd) equal vpt_adam_step_multi's launch-wide values gets its bits.
+// DECOUPLED: p is first multiplied by (float)(1 - (double)lr * (double)wd) (AdamW's param.mul_(1 - lr * weight_decay): the factor formed in double,
+// rounded to float, one rounded multiply), then the coupled update runs with weight_decay = 0.
+template <bool CLIP, bool DECOUPLED>
+__global__ __launch_bounds__(256) void vpt_adam_groups_kernel(const VptAdamTensor* __restrict__ table, const VptAdamGroup* __restrict__ groups, int ntensors,
+                                                              VptAdamArgs h, double bias_correction1) {
+  int lo = 0, hi = ntensors - 1;
+  const long b = blockIdx.x;
+  while (lo < hi) {   // last descriptor with first_block <= b
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid].first_block <= b) lo = mid; else hi = mid - 1;
+  }
+  if (h.skip_flag && *h.skip_flag) return;   // uniform: the whole launch is a no-op when the scaled gradients overflowed
+  const VptAdamTensor t = table[lo];
+  const VptAdamGroup hp = groups[lo];
+  const size_t i0 = ((size_t)(b - t.first_block) * 256 + threadIdx.x) * 4;
+  const float c1 = 1.0f - h.beta1, c2 = 1.0f - h.beta2;
+  const float coef = CLIP ? *h.clip_coef : 1.0f;
+  const float step_size = (float)((double)hp.lr / bias_correction1);
+  const float wd = DECOUPLED ? 0.0f : hp.weight_decay;
+  const float keep = DECOUPLED ? (float)(1.0 - (double)hp.lr * (double)hp.weight_decay) : 1.0f;
+  if (i0 + 4 <= t.n) {   // 16-byte accesses (views may start at any element: unaligned dwordx4 is legal on gfx950)
+    f32x4 p = *(const f32x4*)(t.p + i0), g = *(const f32x4*)(t.g + i0);
+    f32x4 m = *(const f32x4*)(t.m + i0), v = *(const f32x4*)(t.v + i0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (DECOUPLED) p[k] = __fmul_rn(p[k], keep);   // (rounded on its own: never contracted into the update below)
+      const float gk = fmaf(wd, p[k], CLIP ? (g[k] * h.grad_scale) * coef : g[k] * h.grad_scale);
+      m[k] = fmaf(h.beta1, m[k], c1 * gk);
+      v[k] = fmaf(h.beta2, v[k], c2 * gk * gk);
+      const float denom = sqrtf(v[k]) * h.inv_sqrt_bc2 + h.eps;
+      p[k] -= step_size * (m[k] / denom);
+    }
+    *(f32x4*)(t.p + i0) = p;
+    *(f32x4*)(t.m + i0) = m;
+    *(f32x4*)(t.v + i0) = v;
+    return;
+  }
+  for (size_t i = i0; i < t.n; ++i) {   // the tensor's last (partial) group of four
+    const float pk = DECOUPLED ? __fmul_rn(t.p[i], keep) : t.p[i];
+    const float gk = fmaf(wd, pk, CLIP ? (t.g[i] * h.grad_scale) * coef : t.g[i] * h.grad_scale);
+    const float m = fmaf(h.beta1, t.m[i], c1 * gk), v = fmaf(h.beta2, t.v[i], c2 * gk * gk);
+    t.m[i] = m; t.v[i] = v;
+    t.p[i] = pk - step_size * (m / (sqrtf(v) * h.inv_sqrt_bc2 + h.eps));
+  }
+}
+
+extern "C" int vpt_adam_groups_launch(const VptAdamTensor* table_dev, const VptAdamGroup* groups_dev, int ntensors, long total_blocks, const VptAdamArgs* h,
+                                      double bias_correction1, int decoupled, hipStream_t stream) {
+  if (ntensors <= 0 || total_blocks <= 0) return 0;
+  if (total_blocks > 0x7fffffffL) return -2;
+  const dim3 grid((unsigned)total_blocks), block(256);
+  if (h->clip_coef) {
+    if (decoupled) hipLaunchKernelGGL((vpt_adam_groups_kernel<true, true>), grid, block, 0, stream, table_dev, groups_dev, ntensors, *h, bias_correction1);
+    else hipLaunchKernelGGL((vpt_adam_groups_kernel<true, false>), grid, block, 0, stream, table_dev, groups_dev, ntensors, *h, bias_correction1);
+  } else {
+    if (decoupled) hipLaunchKernelGGL((vpt_adam_groups_kernel<false, true>), grid, block, 0, stream, table_dev, groups_dev, ntensors, *h, bias_correction1);
+    else hipLaunchKernelGGL((vpt_adam_groups_kernel<false, false>), grid, block, 0, stream, table_dev, groups_dev, ntensors, *h, bias_correction1);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+
 // ---- overflow check of a loss-scaled step (precision = fp16: the 16-bit gradient buffers carry loss_scale x gradient; a value
 // beyond 65504 anywhere in the chain arrives here as inf / nan).  Same table and block mapping as vpt_adam_multi_kernel; the flag
 // is only ever set (caller zeroes it), so the unordered writes are benign.  th.cuda.amp.GradScaler's found_inf, in one launch.

@@ -46,8 +46,11 @@ class IDMTrainer(TrainerBase):
 
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200, train_cnn: bool = False,
-                 max_grad_norm: Optional[float] = None):
-        """max_grad_norm: global-norm gradient clipping as BCTrainer's (None = off, the default; float("inf") = measure only; a non-finite norm skips
+                 max_grad_norm: Optional[float] = None, trainable=None, param_groups=None, decoupled_weight_decay: bool = False):
+        """trainable / param_groups / decoupled_weight_decay: partial fine-tuning as BCTrainer's (TrainerBase._init_trainer); selecting
+        what this trainer does not train -- `net.lastlayer.*` (unreached), the empty `b_nd`, the CNN side with train_cnn=False -- raises ValueError.
+        With any tensor of the temporal conv or the CNN trainable their whole backward runs and the frozen ones are dropped from the gradients.
+        max_grad_norm: global-norm gradient clipping as BCTrainer's (None = off, the default; float("inf") = measure only; a non-finite norm skips
         the step on the device in both formats).
         policy: lib.policy.InverseActionPolicy on the GPU.  Trainable: `net.img_process.linear.*`, `net.pre_lstm_ln.*` (when configured), every
         `net.recurrent_layer.blocks.*` tensor, `net.final_ln.*`, `pi_head.buttons.*`, `pi_head.camera.*`.  train_cnn=False (default) freezes
@@ -62,7 +65,8 @@ class IDMTrainer(TrainerBase):
         optimizer_state=False: gradients only, no Adam moments.  The fp16 mode uses BCTrainer's loss scaling unchanged (see there): `loss_scale`
         defaults to 256 (1 = off in bf16), the loss gradient is written as loss_scale / temperature x (softmax - one-hot) per frame, the optimiser
         launch un-scales, an overflowed step is skipped on the device, the scale halves then and doubles after `scale_growth_interval` clean steps."""
-        self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm)
+        self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
+                           trainable, param_groups, decoupled_weight_decay)
         # the autograd boundary's counterpart of loss_scale (lib/policy.py:_IDMForwardFn.backward), as BCTrainer's: where the largest incoming
         # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow the boundary detects
         self.autograd_lift, self.autograd_overflows = 256.0, 0
@@ -148,7 +152,9 @@ class IDMTrainer(TrainerBase):
             x0 = ops.conv3d_t5(fr, wfrag, bias, eng.c3d_out, t, stats_out=s0)
             if self.train_cnn:
                 xn, sv = self._cnn_forward_saving(fr, x0=x0, s_x0=s0)
-                cnn_saved.append(sv)
+                if self._cnn_backward:       # (a subset without a CNN-side tensor: the same forward, nothing of it kept)
+                    cnn_saved.append(sv)
+                del sv
                 d32, _ = ops.linear(xn.view(xn.shape[0], -1), w["net.img_process.cnn.dense.w"], 256, splitk=DENSE_SPLITK, tiling=self.dense_tiling)
                 outs.append(d32)
                 del xn
@@ -165,8 +171,8 @@ class IDMTrainer(TrainerBase):
         if mask is not None:
             kept = {h: (mask[h].reshape(m, groups, n).to(torch.uint8).contiguous() if mask.get(h) is not None else None)
                     for h, (groups, n) in (("buttons", eng.button_shape), ("camera", eng.camera_shape))}
-        return dict(trunk, m=m, bsz=bsz, t=t, dev=img_u8.device, d=d, lb=lb,
-                    lp_b=lps["buttons"], lp_c=lps["camera"], mask=kept, cnn_saved=cnn_saved, cnn_step=step)
+        return self._release_unread(dict(trunk, m=m, bsz=bsz, t=t, dev=img_u8.device, d=d, lb=lb,
+                                         lp_b=lps["buttons"], lp_c=lps["camera"], mask=kept, cnn_saved=cnn_saved, cnn_step=step))
 
     def _attention_backward(self, S, l, datt, g):
         """Mask "none": no memory, no relative-position bias -- nothing of the attention itself is trained."""
@@ -182,7 +188,7 @@ class IDMTrainer(TrainerBase):
         CNN's finish step."""
         P = {n: p.detach() for n, p in self.params.items()}
         g, dd = self._trunk_backward(S, dz, P)
-        if self.train_cnn:
+        if self.train_cnn and self._cnn_backward:
             m, t, cnn_saved, step = S["m"], S["t"], S["cnn_saved"], S["cnn_step"]
             acc = self._cnn_backward_begin(P)
             c3d = (torch.zeros_like(P["net.conv3d_layer.layer.weight"], dtype=torch.float32), torch.zeros_like(P["net.conv3d_layer.layer.bias"], dtype=torch.float32))
@@ -194,6 +200,9 @@ class IDMTrainer(TrainerBase):
                 del sv, dx0
             self._cnn_backward_finish(acc, P, g)
             g["net.conv3d_layer.layer.weight"], g["net.conv3d_layer.layer.bias"] = c3d
+            if self._subset is not None:     # no cut inside the CNN: the frozen tensors of that side are dropped
+                for n in [n for n in g if n.startswith(_FROZEN) and n not in self._subset]:
+                    del g[n]
         return g
 
     @torch.no_grad()

@@ -242,6 +242,34 @@ def _unlift_(eng, g, scale) -> bool:
     return True
 
 
+MAX_GRAD_ENGINES = 4      # gradient engines a policy keeps for its autograd boundary (one per set of parameters that require grad)
+
+
+def _grad_engine(policy, trainer_cls, named, cnn_prefixes):
+    """The gradient engine of a gradient-enabled call: a trainer_cls(policy, optimizer_state=False) chosen by the SET of parameters that require
+    grad.  When every tensor the trainer's rule covers requires grad the key is train_cnn -- True / False, one engine each, built with default
+    arguments: what the boundary has always used.  After the reference's freezing idiom (`p.requires_grad = False`, or requires_grad_(False) on
+    a module) the engine is built with trainable=<the names that still require grad>, so loss.backward() runs the backward that stops where
+    training stops (trainer_base.TrainerBase._trunk_backward) and frozen inputs get None.  (A value head is no part of either trainer's rule at
+    the boundary: its gradient is the node's own business, _PolicyForwardFn.backward.)  At most MAX_GRAD_ENGINES are kept; the oldest goes first."""
+    params = dict(named)
+    train_cnn = any(p.requires_grad for n, p in named if n.startswith(cnn_prefixes))
+    rule = trainer_cls.rule_trainable(params, train_cnn)
+    req = [n for n in rule if params[n].requires_grad]
+    if len(req) == len(rule):
+        key, selection = train_cnn, None
+    else:       # (only a value head left to train: the walk still ends at the heads, whose own gradients autograd then discards)
+        selection = req or [n for n in rule if n.startswith("pi_head.")]
+        key = tuple(selection)
+    engines = policy._grad_engines
+    eng = engines.get(key)
+    if eng is None:
+        eng = engines[key] = trainer_cls(policy, train_cnn=train_cnn, optimizer_state=False, trainable=selection)
+        while len(engines) > MAX_GRAD_ENGINES:
+            policy._grad_overflows_evicted += engines.pop(next(iter(engines))).autograd_overflows
+    return eng
+
+
 class _PolicyForwardFn(torch.autograd.Function):
     """The differentiable boundary: MinecraftAgentPolicy.forward as ONE autograd node whose backward is the hand-written
     HIP backward of training.py (every layer, CNN included).  That is what lets the reference's own training loop --
@@ -283,10 +311,11 @@ class _PolicyForwardFn(torch.autograd.Function):
                 return none
             dz = ops.heads_logprob_backward(S["lp_b"], S["lp_c"], gb, gc, gv, S["ldz"], eng.engine.cfg["temperature"],
                                             mask_buttons=S["mask"]["buttons"], mask_camera=S["mask"]["camera"], dtype=eng.dtype, grad_scale=scale)
-            g = eng.backward_from(S, dz, value_grads=gv is not None)
+            needs = ctx.needs_input_grad[7:]
+            g = eng.backward_from(S, dz, value_grads=gv is not None and any(nd for n, nd in zip(ctx.names, needs) if n.startswith("value_head.linear.")))
             if not _unlift_(eng, g, scale):
                 return none
-        grads = tuple(g[n].reshape(shape) if n in g else None for n, shape in zip(ctx.names, ctx.param_shapes))
+        grads = tuple(g[n].reshape(shape) if nd and n in g else None for n, nd, shape in zip(ctx.names, needs, ctx.param_shapes))
         return (None, None, None, None, None, None, None) + grads
 
 
@@ -323,7 +352,7 @@ class _IDMForwardFn(torch.autograd.Function):
             g = eng.backward_from(S, dz)
             if not _unlift_(eng, g, scale):
                 return none
-        grads = tuple(g[n].reshape(shape) if n in g else None for n, shape in zip(ctx.names, ctx.param_shapes))
+        grads = tuple(g[n].reshape(shape) if nd and n in g else None for n, nd, shape in zip(ctx.names, ctx.needs_input_grad[4:], ctx.param_shapes))
         return (None, None, None, None) + grads
 
 
@@ -347,6 +376,7 @@ class MinecraftAgentPolicy(nn.Module):
         import os
         self._auto_graph = dict(enabled=os.environ.get("VPT_STEP_GRAPH", "1") != "0", batch=None, count=0)
         self._grad_engines = {}
+        self._grad_overflows_evicted = 0
         self._episode_starts = "chunk"
 
     @property
@@ -392,7 +422,7 @@ class MinecraftAgentPolicy(nn.Module):
         incoming gradient was non-finite.  A gradient-accumulation loop (the reference's 8 x backward then optimizer.step(),
         behavioural_cloning.py:107-122) reads it before and after its backwards and skips optimizer.step() when it moved -- what
         torch.cuda.amp.GradScaler.step does.  Always 0 in bf16."""
-        return sum(e.autograd_overflows for e in self._grad_engines.values())
+        return self._grad_overflows_evicted + sum(e.autograd_overflows for e in self._grad_engines.values())
 
     # ---- engine plumbing --------------------------------------------------------------------
     def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .half(): parameters may be re-created
@@ -639,13 +669,11 @@ class MinecraftAgentPolicy(nn.Module):
 
     def _forward_differentiable(self, img, first, state_in, mask=None):
         """Gradient-enabled call (the reference's get_output_for_observation is, lib/policy.py:287-305): same kernels, every
-        activation kept for the backward, outputs attached to the autograd graph through _PolicyForwardFn."""
+        activation kept for the backward, outputs attached to the autograd graph through _PolicyForwardFn.  The engine follows the set of
+        parameters that require grad (_grad_engine): with part of the model frozen the backward stops where training stops."""
         from ..training import BCTrainer
         named = [(n, p) for n, p in self.named_parameters()]
-        train_cnn = any(p.requires_grad for n, p in named if n.startswith("net.img_process.cnn."))
-        eng = self._grad_engines.get(train_cnn)
-        if eng is None:
-            eng = self._grad_engines[train_cnn] = BCTrainer(self, train_cnn=train_cnn, optimizer_state=False)
+        eng = _grad_engine(self, BCTrainer, named, "net.img_process.cnn.")
         eng.episode_starts = self._episode_starts
         names = [n for n, _ in named]
         out = _PolicyForwardFn.apply(self, eng, img, first, state_in, mask, names, *[p for _, p in named])
@@ -737,6 +765,7 @@ class InverseActionPolicy(nn.Module):
         self._engine = IDMEngine(self._cfg, (bt.size, bt.eltype.n), (ct.size, ct.eltype.n), precision=precision)
         self._packed_key = None
         self._grad_engines = {}
+        self._grad_overflows_evicted = 0
 
     @property
     def precision(self) -> str:
@@ -745,7 +774,7 @@ class InverseActionPolicy(nn.Module):
     @property
     def grad_overflows(self) -> int:
         """How many backward passes through this model returned NO gradients (MinecraftAgentPolicy.grad_overflows).  Always 0 in bf16."""
-        return sum(e.autograd_overflows for e in self._grad_engines.values())
+        return self._grad_overflows_evicted + sum(e.autograd_overflows for e in self._grad_engines.values())
 
     def set_precision(self, precision: str):
         if precision != self._engine.precision:
@@ -801,13 +830,11 @@ class InverseActionPolicy(nn.Module):
         """Gradient-enabled call: IDMTrainer's saving forward, outputs attached to the autograd graph through _IDMForwardFn.  The CNN and the temporal
         conv are trained (train_cnn) exactly when one of their parameters requires grad; with them frozen (`requires_grad_(False)`) the part in front
         of the dense layer's output runs as in inference and the log-probs equal the no_grad forward's bit for bit.  Parameters the function does
-        not reach (`net.lastlayer.*`, the empty `b_nd`, a frozen CNN) get no gradient (None); `r_layer.*` gets exact zeros, as from IDMTrainer."""
+        not reach (`net.lastlayer.*`, the empty `b_nd`, a frozen CNN) get no gradient (None); `r_layer.*` gets exact zeros, as from IDMTrainer.
+        Any other frozen parameter gets None too, and the backward stops where training stops (_grad_engine)."""
         from ..idm_training import IDMTrainer
         named = list(self.named_parameters())
-        train_cnn = any(p.requires_grad for n, p in named if n.startswith(("net.conv3d_layer.", "net.img_process.cnn.")))
-        eng = self._grad_engines.get(train_cnn)
-        if eng is None:
-            eng = self._grad_engines[train_cnn] = IDMTrainer(self, train_cnn=train_cnn, optimizer_state=False)
+        eng = _grad_engine(self, IDMTrainer, named, ("net.conv3d_layer.", "net.img_process.cnn."))
         lp_b, lp_c = _IDMForwardFn.apply(eng, img, mask, [n for n, _ in named], *[p for _, p in named])
         return {"buttons": lp_b, "camera": lp_c}
 

@@ -868,6 +868,54 @@ def adam_step_multi_(params, grads, exp_avgs, exp_avg_sqs, step, lr, beta1=0.9, 
     return table   # (norm_out too outlives the enqueue: the Adam launch reads norm_out[1] on the device; a scratch one is freed in stream order)
 
 
+def adam_step_groups_(params, grads, exp_avgs, exp_avg_sqs, step, lrs, weight_decays, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0,
+                      decoupled=False, found_inf=None, max_grad_norm=None, norm_out=None, per_tensor_norms=None):
+    """adam_step_multi_ with ONE (lr, weight_decay) PER TENSOR, still one launch (vpt_adam_step_groups): torch.optim.Adam over parameter groups,
+    and with decoupled=True torch.optim.AdamW's decay, p *= 1 - lr * wd before a coupled update with weight_decay = 0.
+    lrs, weight_decays: sequences of len(params) floats (rounded to fp32 as a launch argument would be); they travel as a device array next to
+    the table.  A tensor whose (lr, wd) are adam_step_multi_'s launch-wide values gets that launch's bits (the step size is the same double
+    expression on the fp32 lr, formed in the kernel).  found_inf / max_grad_norm / norm_out / per_tensor_norms: as adam_step_multi_, with the same
+    launches in front (vpt_grads_nonfinite_multi, or vpt_grad_norm_multi which replaces it); the norm is ONE global norm over all groups.
+    ValueError on a length mismatch and on tensors that are not contiguous fp32.  Returns (table, hyper array): keep them until the launch is enqueued."""
+    import numpy as np
+    lists = [list(params), list(grads), list(exp_avgs), list(exp_avg_sqs), list(lrs), list(weight_decays)]
+    n_t = len(lists[0])
+    if any(len(x) != n_t for x in lists[1:]):
+        raise ValueError(f"adam_step_groups_: one entry per tensor everywhere, got lengths {[len(x) for x in lists]} "
+                         "(params, grads, exp_avgs, exp_avg_sqs, lrs, weight_decays)")
+    params, grads, exp_avgs, exp_avg_sqs, lrs, weight_decays = lists
+    for i in range(n_t):
+        for t, nme in ((params[i], "param"), (grads[i], "grad"), (exp_avgs[i], "exp_avg"), (exp_avg_sqs[i], "exp_avg_sq")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"adam_step_groups_: {nme} {i} must be a contiguous fp32 tensor")
+            if t.numel() != params[i].numel():
+                raise ValueError(f"adam_step_groups_: {nme} {i} has {t.numel()} elements, its parameter {params[i].numel()}")
+    if n_t == 0:
+        return None
+    _chk(found_inf, torch.int32, "found_inf")
+    table, blk, numel = _adam_table(grads, params, exp_avgs, exp_avg_sqs)
+    rec = np.zeros(n_t, dtype=[("lr", "<f4"), ("wd", "<f4")])      # VptAdamGroup, record i for table entry i
+    rec["lr"], rec["wd"] = np.asarray(lrs, dtype=np.float64), np.asarray(weight_decays, dtype=np.float64)
+    hyper = torch.from_numpy(rec.view(np.uint8)).to(table.device, non_blocking=False)
+    clip_coef = None
+    if found_inf is not None:
+        found_inf.zero_()
+    if max_grad_norm is None:
+        if found_inf is not None:
+            _call("vpt_grads_nonfinite_multi", dict(bytes=4.0 * numel), ptr(table), n_t, blk, ptr(found_inf), _stream())
+    else:
+        if norm_out is None:
+            norm_out = torch.empty(4, dtype=torch.float32, device=table.device)
+        _chk(norm_out, torch.float32, "norm_out")
+        _chk(per_tensor_norms, torch.float32, "per_tensor_norms")
+        assert norm_out.numel() >= 4 and norm_out.is_contiguous() and (per_tensor_norms is None or per_tensor_norms.numel() >= n_t)
+        _grad_norm_launch(table, n_t, blk, numel, grad_scale, max_grad_norm, norm_out, per_tensor_norms, found_inf)
+        clip_coef = norm_out[1:]
+    _call("vpt_adam_step_groups", dict(bytes=28.0 * numel), ptr(table), ptr(hyper), n_t, blk, int(step), ctypes.c_float(beta1), ctypes.c_float(beta2),
+          ctypes.c_float(eps), ctypes.c_float(grad_scale), 1 if decoupled else 0, ptr(found_inf), ptr(clip_coef), _stream())
+    return table, hyper
+
+
 def grad_accumulate_(accs, grads):
     """accs[i] += grads[i] for lists of contiguous fp32 tensors in ONE launch (vpt_grad_accumulate_multi): one fp32 add per element in the table
     and block mapping of adam_step_multi_, no reductions, no atomics -- torch's `acc + g`, bit for bit.  inf / nan go through the sum.

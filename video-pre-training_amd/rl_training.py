@@ -46,7 +46,8 @@ class PPOTrainer(BCTrainer):
         clone_coef, aux_value_coef: the auxiliary phase's weights of KL(pi_old || pi) and of the squared value error (aux_step; None: value_coef);
         nothing outside the aux_* methods reads them.
         bc_kwargs: BCTrainer's arguments (lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, episode_starts,
-        max_grad_norm -- global-norm gradient clipping, off by default; see there).
+        max_grad_norm -- global-norm gradient clipping, off by default; trainable, param_groups, decoupled_weight_decay -- partial fine-tuning, e.g.
+        trainable=["pi_head", "value_head"]; see there).
         The value head's Linear trains here (BCTrainer excludes it: it has no gradient under the BC loss)."""
         super().__init__(policy, **bc_kwargs)
         self.clip, self.kl_coef, self.entropy_coef, self.value_coef = float(clip), float(kl_coef), float(entropy_coef), float(value_coef)

@@ -8,7 +8,10 @@ The two trunks differ in five places, each a class attribute or a hook of Traine
     head_params      the rows of the fused head matrix (BC: buttons, camera, value; IDM: buttons, camera)
     has_lastlayer    net.lastlayer between x_trunk and final_ln (BC)
     final_ln_relu    final_ln reads relu(x_trunk) (IDM)
-The CNN's part of either pass stays with cnn_training.CnnTrainingMixin and the trainers' own chunk loops."""
+The CNN's part of either pass stays with cnn_training.CnnTrainingMixin and the trainers' own chunk loops.
+
+Partial fine-tuning lives here too: which tensors train (select_trainable, resolve_param_groups: host code on names), the trunk
+backward that stops at the first unit holding a trainable tensor, and the per-group Adam launch of the optimiser tail."""
 from typing import Dict, List, Optional
 
 import torch
@@ -42,6 +45,81 @@ def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], wei
     return dx32, dx16, dw
 
 
+# ---- which tensors train: name selection and parameter groups, plain host code on names only ---------------------------------
+def name_matches(selector: str, name: str) -> bool:
+    """A selector is an exact parameter name or a module prefix ending at a `.` boundary: "net.recurrent_layer.blocks.1" matches
+    "net.recurrent_layer.blocks.1.mlp0.layer.weight", never "net.recurrent_layer.blocks.10...".  (A trailing "." is accepted and means the same.)"""
+    s = selector[:-1] if selector.endswith(".") else selector
+    return name == s or name.startswith(s + ".")
+
+
+def _selector_list(selection, what: str) -> List[str]:
+    sel = [selection] if isinstance(selection, str) else list(selection)
+    bad = [s for s in sel if not isinstance(s, str) or not s.strip(".")]
+    if bad:
+        raise ValueError(f"{what}: selectors must be non-empty parameter names or module prefixes, got {bad!r}")
+    return sel
+
+
+def select_trainable(names: List[str], rule, selection, who: str = "trainer") -> List[str]:
+    """The effective trainable set, in the order of `names`: the trainer's own rule(name) AND the selection.
+    selection: None (the rule alone), an iterable of selector strings (name_matches) or a callable name -> bool.
+    ValueError, naming the offenders: a string that matches no parameter; a string that selects a tensor the rule excludes; an empty result.
+    (A callable is a filter: what it accepts outside the rule is left out silently -- `lambda n: True` is the rule's own set.)"""
+    names = list(names)
+    ruled = [n for n in names if rule(n)]
+    if selection is None:
+        return ruled
+    if callable(selection):
+        out = [n for n in ruled if selection(n)]
+    else:
+        sel = _selector_list(selection, f"{who}(trainable=)")
+        unmatched = [s for s in sel if not any(name_matches(s, n) for n in names)]
+        if unmatched:
+            raise ValueError(f"{who}(trainable=): {unmatched!r} match no parameter")
+        picked = [n for n in names if any(name_matches(s, n) for s in sel)]
+        ruled_set = set(ruled)
+        excluded = [n for n in picked if n not in ruled_set]
+        if excluded:
+            raise ValueError(f"{who}(trainable=): this trainer does not train {excluded[:6]!r}{' ...' if len(excluded) > 6 else ''} "
+                             f"({len(excluded)} selected tensors are outside its own rule)")
+        out = picked
+    if not out:
+        raise ValueError(f"{who}(trainable=): the selection leaves no trainable parameter")
+    return out
+
+
+def resolve_param_groups(names: List[str], trainable: List[str], param_groups, who: str = "trainer"):
+    """param_groups = [dict(params=<selector strings>, lr_scale=1.0, weight_decay=<the trainer's>), ...] ->
+    (the groups normalised to dict(params=[strings], lr_scale=float, weight_decay=float | None) -- what state_dict() carries --,
+     {trainable name: index of its group}).  Names in no group use the trainer's values.  ValueError: an unknown key, a selector that matches no
+    parameter, a group naming a tensor that is not trainable, a name in two groups."""
+    groups, owner = [], {}
+    tset = set(trainable)
+    for gi, grp in enumerate(param_groups or ()):
+        if not isinstance(grp, dict) or "params" not in grp or set(grp) - {"params", "lr_scale", "weight_decay"}:
+            raise ValueError(f"{who}(param_groups=): group {gi} must be dict(params=..., lr_scale=..., weight_decay=...), got {grp!r}")
+        sel = _selector_list(grp["params"], f"{who}(param_groups=)[{gi}]")
+        unmatched = [s for s in sel if not any(name_matches(s, n) for n in names)]
+        if unmatched:
+            raise ValueError(f"{who}(param_groups=): group {gi}: {unmatched!r} match no parameter")
+        picked = [n for n in names if any(name_matches(s, n) for s in sel)]
+        frozen = [n for n in picked if n not in tset]
+        if frozen:
+            raise ValueError(f"{who}(param_groups=): group {gi} names tensors that are not trainable: {frozen[:6]!r}{' ...' if len(frozen) > 6 else ''}")
+        twice = [n for n in picked if n in owner]
+        if twice:
+            raise ValueError(f"{who}(param_groups=): {twice[:6]!r} are in group {owner[twice[0]]} and in group {gi}")
+        lr_scale = float(grp.get("lr_scale", 1.0))
+        wd = grp.get("weight_decay")
+        if not (lr_scale >= 0.0 and lr_scale != float("inf")) or (wd is not None and not (float(wd) >= 0.0 and float(wd) != float("inf"))):
+            raise ValueError(f"{who}(param_groups=): group {gi}: lr_scale and weight_decay must be finite and non-negative, got {grp!r}")
+        for n in picked:
+            owner[n] = gi
+        groups.append(dict(params=sel, lr_scale=lr_scale, weight_decay=None if wd is None else float(wd)))
+    return groups, owner
+
+
 class TrainerBase(CnnTrainingMixin):
     fused_qkv = "qkvr"           # the fused projection's name in the engine's packed weights and in saved[l]; "qkv": without r_layer (mask "none")
     head_params = ("pi_head.buttons.linear_layer", "pi_head.camera.linear_layer", "value_head.linear")      # the fused head matrix, row blocks in order
@@ -49,9 +127,28 @@ class TrainerBase(CnnTrainingMixin):
     final_ln_relu = False        # final_ln reads relu(its input)
     max_grad_norm = None         # None: no clipping (what the reference's script does); 5.0: what it meant; float("inf"): measure, never clip
     last_grad_norm = None        # fp32 device scalar of the last step that measured (max_grad_norm set)
+    # partial fine-tuning.  The class values are the default-constructed trainer's: everything its own rule trains, one group
+    _subset = None               # None: trainable=None, today's set on today's code path; else the frozenset of the effective names
+    _cut = -1                    # the trunk unit (see _unit_level) the backward stops at; -1: it runs down to dd
+    _cnn_backward = True         # with train_cnn: some CNN-side tensor is trainable, so the CNN activations are kept and its backward runs
+    param_groups = ()            # the normalised groups of resolve_param_groups
+    _group_of: Dict[str, int] = {}
+    decoupled_weight_decay = False
 
-    def _init_trainer(self, policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm):
-        """The state every trainer keeps (the constructors' docstrings say what the arguments mean)."""
+    def _init_trainer(self, policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
+                      trainable=None, param_groups=None, decoupled_weight_decay=False):
+        """The state every trainer keeps (the constructors' docstrings say what the arguments mean).
+        trainable / param_groups / decoupled_weight_decay: partial fine-tuning, shared by the three trainers --
+        trainable: None (default: the trainer's own rule, on the code path that has always run), an iterable of strings -- exact parameter names
+        or module prefixes ending at a `.` boundary, e.g. "pi_head", "net.lastlayer", "net.recurrent_layer.blocks.3" -- or a callable name -> bool.
+        The effective set is the rule AND the selection (select_trainable: ValueError on a string that matches nothing, on a string that selects
+        what the rule excludes, on an empty set).  self.trainable, the Adam moments, the arenas, the norm and the clip cover the effective set only.
+        The backward then stops at the first trunk unit (in forward order: net.img_process.linear, net.pre_lstm_ln, the blocks, net.lastlayer,
+        net.final_ln, the heads) that holds a trainable tensor -- and inside that unit where nothing trainable is left --, launches no wgrad GEMM
+        and no bias sum for a frozen tensor above it, and the saving forward keeps nothing the shortened backward does not read.  Inside the CNN
+        nothing is cut: if any CNN tensor is trainable its whole backward runs and the frozen CNN tensors' gradients are dropped.
+        param_groups: [dict(params=<strings as above>, lr_scale=1.0, weight_decay=<the trainer's>), ...]; lr_scale multiplies self.lr at step time.
+        decoupled_weight_decay: torch.optim.AdamW's decay instead of Adam's L2 term.  Either makes step() use ops.adam_step_groups_ (one launch)."""
         self.train_cnn = bool(train_cnn)
         self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
         self.policy = policy
@@ -64,12 +161,47 @@ class TrainerBase(CnnTrainingMixin):
         self.step_count = 0
         self._cnn_flags_from_env()       # gated_dgrad, fused_pool, fold_n_backward, fold_n_backward0 (cnn_training.py)
         self.params: Dict[str, torch.nn.Parameter] = dict(policy.named_parameters())
-        self.trainable = [n for n in self.params if self._is_trainable(n)]
-        self.m = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
+        names = self._selectable_names()
+        self.trainable = select_trainable(list(self.params) if trainable is None else names, self._is_trainable, trainable, type(self).__name__)
+        if trainable is not None:
+            self._subset = frozenset(self.trainable)
+            self._cut = min(self._unit_level(n) for n in self.trainable)
+            self._cnn_backward = self.train_cnn and self._cut < 0
+        self.param_groups, self._group_of = resolve_param_groups(names, self.trainable, param_groups, type(self).__name__)
+        self.decoupled_weight_decay = bool(decoupled_weight_decay)
+        self.m ={n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
         self.v = {n: torch.zeros_like(self.params[n], dtype=torch.float32) for n in self.trainable} if optimizer_state else {}
 
     def _is_trainable(self, name: str) -> bool:
+        """The trainer's own rule (reads self.train_cnn and self.params only)."""
         raise NotImplementedError
+
+    @classmethod
+    def rule_trainable(cls, params: Dict[str, torch.Tensor], train_cnn: bool) -> List[str]:
+        """The names a cls(policy, train_cnn=train_cnn) trains by default, without building one (the autograd boundary compares them with the
+        parameters that require grad)."""
+        probe = object.__new__(cls)
+        probe.train_cnn, probe.params = bool(train_cnn), params
+        return [n for n in params if probe._is_trainable(n)]
+
+    def _selectable_names(self) -> List[str]:
+        """The names a selector string is matched against: the parameters minus what no optimiser could ever move -- an empty tensor (the IDM's
+        b_nd [10, 0]) and the value normaliser's statistics (Parameters only so that they travel with the state_dict; they move by update()).
+        So "value_head" under PPOTrainer and a whole block under IDMTrainer select what there is to train instead of raising."""
+        return [n for n, p in self.params.items() if p.numel() and not n.startswith("value_head.normalizer.")]
+
+    def _unit_level(self, name: str) -> int:
+        """The trunk unit a parameter belongs to, in forward order: 0 net.img_process.linear, 1 net.pre_lstm_ln, 2 + l block l, 2 + n net.lastlayer,
+        3 + n net.final_ln, 4 + n the fused heads; -1: in front of the trunk (the CNN, the IDM's temporal conv)."""
+        n = self.engine.cfg["n_layers"]
+        blocks = "net.recurrent_layer.blocks."
+        if name.startswith(blocks):
+            return 2 + int(name[len(blocks):].split(".", 1)[0])
+        for prefix, level in (("net.img_process.linear.", 0), ("net.pre_lstm_ln.", 1), ("net.lastlayer.", 2 + n), ("net.final_ln.", 3 + n),
+                              ("pi_head.", 4 + n), ("value_head.", 4 + n)):
+            if name.startswith(prefix):
+                return level
+        return -1
 
     @staticmethod
     def _checked_max_grad_norm(max_grad_norm):
@@ -85,10 +217,17 @@ class TrainerBase(CnnTrainingMixin):
         """Optimizer state next to the policy's own `.weights` state_dict (behavioural_cloning.py:131-132 saves only the
         latter): Adam moments keyed by the reference's parameter names, the step count and the hyper-parameters."""
         self._need_optimizer_state()
-        return dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
-                    loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
-                    exp_avg={n: t.detach().clone() for n, t in self.m.items()},
-                    exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
+        sd = dict(step=self.step_count, lr=self.lr, weight_decay=self.wd, betas=tuple(self.betas), eps=self.eps,
+                  loss_scale=self.loss_scale, train_cnn=self.train_cnn, max_grad_norm=self.max_grad_norm,
+                  exp_avg={n: t.detach().clone() for n, t in self.m.items()},
+                  exp_avg_sq={n: t.detach().clone() for n, t in self.v.items()})
+        # partial fine-tuning: what a default-constructed trainer does not have it does not write (its dict is the one it always wrote)
+        if self._subset is not None:
+            sd["trainable"] = list(self.trainable)
+        if self.param_groups or self.decoupled_weight_decay:
+            sd["param_groups"] = [dict(g, params=list(g["params"])) for g in self.param_groups]
+            sd["decoupled_weight_decay"] = self.decoupled_weight_decay
+        return sd
 
     def _need_optimizer_state(self):
         if not self.m and self.trainable:
@@ -102,6 +241,9 @@ class TrainerBase(CnnTrainingMixin):
             self.max_grad_norm = self._checked_max_grad_norm(sd["max_grad_norm"])
         if set(sd["exp_avg"]) != set(self.m):
             raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
+        if "param_groups" in sd:            # (a dict without them leaves the constructor's groups and flag in place)
+            self.param_groups, self._group_of = resolve_param_groups(self._selectable_names(), self.trainable, sd["param_groups"], type(self).__name__)
+            self.decoupled_weight_decay = bool(sd.get("decoupled_weight_decay", False))
         self.step_count = int(sd["step"])
         self.lr, self.wd, self.betas, self.eps = sd["lr"], sd["weight_decay"], tuple(sd["betas"]), sd["eps"]
         for n in self.m:
@@ -247,10 +389,20 @@ class TrainerBase(CnnTrainingMixin):
         found_inf = torch.zeros(1, dtype=torch.int32, device=device) if (self.scaled or clip) else None
         per = torch.empty(len(names), dtype=torch.float32, device=device) if (clip and metrics is not None) else None
         norm_out = torch.empty(4, dtype=torch.float32, device=device) if clip else None
-        ops.adam_step_multi_([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
-                             [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names], self.step_count + 1,
-                             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
-                             grad_scale=grad_scale, found_inf=found_inf, max_grad_norm=self.max_grad_norm, norm_out=norm_out, per_tensor_norms=per)
+        tensors = ([self.params[n].data.view(-1) for n in names], [grads[n].contiguous().view(-1) for n in names],
+                   [self.m[n].view(-1) for n in names], [self.v[n].view(-1) for n in names])
+        if self.param_groups or self.decoupled_weight_decay:
+            # parameter groups / AdamW decay: the same launches in front, then ONE vpt_adam_step_groups launch with (lr, weight_decay) per tensor;
+            # lr_scale multiplies the lr of THIS step (a host schedule that assigns trainer.lr keeps working)
+            grp = [self.param_groups[self._group_of[n]] if n in self._group_of else None for n in names]
+            ops.adam_step_groups_(*tensors, self.step_count + 1, [self.lr if g_ is None else self.lr * g_["lr_scale"] for g_ in grp],
+                                  [self.wd if g_ is None or g_["weight_decay"] is None else g_["weight_decay"] for g_ in grp],
+                                  beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, grad_scale=grad_scale, decoupled=self.decoupled_weight_decay,
+                                  found_inf=found_inf, max_grad_norm=self.max_grad_norm, norm_out=norm_out, per_tensor_norms=per)
+        else:
+            ops.adam_step_multi_(*tensors, self.step_count + 1,
+                                 lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.wd,
+                                 grad_scale=grad_scale, found_inf=found_inf, max_grad_norm=self.max_grad_norm, norm_out=norm_out, per_tensor_norms=per)
         if clip and names:
             self.last_grad_norm = norm_out[0]
             if metrics is not None:
@@ -295,9 +447,23 @@ class TrainerBase(CnnTrainingMixin):
             _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=dt)
             _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True, **linear_kw)
             xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, **linear_kw)
-            saved.append(dict(own, x=x, x1b=x1b, att=att, x2=x2, hb=hb, h2=h2, **{fq: qkv}))
+            # a block below the cut is never walked by the backward: its activations go as the forward leaves them (None keeps the index)
+            saved.append(dict(own, x=x, x1b=x1b, att=att, x2=x2, hb=hb, h2=h2, **{fq: qkv}) if 2 + l >= self._cut else None)
             x = xo
+        if self._cut > 0:       # the backward stops above ImgObsProcess.linear (and, from 2 on, above pre_lstm_ln): their inputs are not read
+            dn = x_lin16 = None
+            if self._cut > 1:
+                x_pre = None
         return dict(dn=dn, x_lin16=x_lin16, x_pre=x_pre, saved=saved, x_trunk=x)
+
+    def _release_unread(self, S: dict) -> dict:
+        """Drop from a forward_saving dict what a backward cut above it does not read: `d` (ImgObsProcess.linear's LayerNorm), `xb` / `y16`
+        (net.lastlayer), `y` (net.final_ln's input where there is a lastlayer).  The default set (cut -1) keeps everything."""
+        n = self.engine.cfg["n_layers"]
+        for key, level in (("d", 0), ("xb", 2 + n), ("y16", 2 + n), ("y", 3 + n)):
+            if self._cut > level and key in S:
+                S[key] = None
+        return S
 
     def _attention_backward(self, S: dict, l: int, datt: torch.Tensor, g: Dict[str, torch.Tensor]) -> torch.Tensor:
         """datt fp32 [M, hid] -> d loss / d (the fused projection's output of block l); adds to `g` what the attention itself trains."""
@@ -309,91 +475,166 @@ class TrainerBase(CnnTrainingMixin):
         lastlayer (has_lastlayer) -> per block, last to first: mlp1, mlp0, its LayerNorm (+ skip), proj, _attention_backward, the fused projection's
         GEMM (+ skip), pre_r_ln -> pre_lstm_ln -> ImgObsProcess.linear and its LayerNorm.  P: the parameters, detached.
         value_grads: also return the value head's gradients (non-zero only when dz's value column is).  debug: a dict that receives clones of the
-        intermediate gradients (tools/bc_grad_diag.py)."""
+        intermediate gradients (tools/bc_grad_diag.py).
+        With a trainable subset (trainable=) the SAME launches run in the same order with the same operands, minus those nothing
+        trainable needs: a wgrad GEMM whose weights are all frozen (a fused GEMM -- heads, q/k/v/r -- loses it only when every tensor in it is),
+        the bias sum of a frozen bias, and every launch below the last trainable tensor -- the walk returns (g, None) there, so the dgrad into the
+        unit below the cut is never launched.  A LayerNorm backward that only carries the gradient on keeps its launch; its gain / bias sums are
+        discarded.  g holds exactly the trainable names, each bit-equal to the full run's tensor.  The default set takes every branch."""
         cfg = self.engine.cfg
         dev, saved, x_trunk = S["dev"], S["saved"], S["x_trunk"]
-        hid, ratio = cfg["hidsize"], cfg["pointwise_ratio"]
+        hid, ratio, n_layers = cfg["hidsize"], cfg["pointwise_ratio"], cfg["n_layers"]
         nq, r_fused = self.engine.n_qkvr, self.fused_qkv == "qkvr"
         pl = "net.img_process.linear."
+        sub, cut = self._subset, self._cut
+        want = (lambda name: True) if sub is None else sub.__contains__
+        any_of = lambda *names: any(want(n_) for n_ in names)
         g: Dict[str, torch.Tensor] = {}
         zeros = lambda n_: torch.zeros(n_, dtype=torch.float32, device=dev)
+
+        def keep(name, tensor):
+            if want(name):
+                g[name] = tensor
+
+        def layernorm_backward(x, prefix, dy, **kw):      # prefix + "weight" / "bias"; a frozen LayerNorm's sums are computed and dropped
+            dgain, dbias = zeros(x.shape[1]), zeros(x.shape[1])
+            dx_ = ops.layernorm_backward(x, P[prefix + "weight"], dy, dgain, dbias, **kw)
+            keep(prefix + "weight", dgain); keep(prefix + "bias", dbias)
+            return dx_
+
         # heads (one fused GEMM over head_params' row blocks): dlat, dW, db
         hw = [P[h + ".weight"] for h in self.head_params]
         nb, nc = hw[0].shape[0], hw[1].shape[0]
         wh = torch.cat(hw, 0)
         nh = wh.shape[0]
-        dlat, _, dwh = linear_backward(dz, nh, S["lb"], wh)
+        bw, cw, bb, cb = ("pi_head.buttons.linear_layer.weight", "pi_head.camera.linear_layer.weight",
+                          "pi_head.buttons.linear_layer.bias", "pi_head.camera.linear_layer.bias")
+        # the value head: the caller's choice where the trainer's rule leaves it out (BCTrainer, the autograd boundary), else a tensor like any other
+        vw, vb = [value_grads and (want(n_) or not self._is_trainable(n_)) for n_ in ("value_head.linear.weight", "value_head.linear.bias")]
+        below = cut < 4 + n_layers
+        dlat, _, dwh = linear_backward(dz, nh, S["lb"], wh, need_dx=below, need_dw=vw or any_of(bw, cw))
         if debug is not None:
             debug['dlatent'] = dlat.clone(); debug['latent'] = S["lb"].float().clone()
-        dbh = zeros(nh)
-        ops.column_sum_(dbh, dz, nh)
-        g["pi_head.buttons.linear_layer.weight"], g["pi_head.camera.linear_layer.weight"] = dwh[:nb], dwh[nb:nb + nc]
-        g["pi_head.buttons.linear_layer.bias"], g["pi_head.camera.linear_layer.bias"] = dbh[:nb], dbh[nb:nb + nc]
-        if value_grads:
-            g["value_head.linear.weight"], g["value_head.linear.bias"] = dwh[nb + nc:nh].clone(), dbh[nb + nc:nh].clone()
+        if vb or any_of(bb, cb):
+            dbh = zeros(nh)
+            ops.column_sum_(dbh, dz, nh)
+            keep(bb, dbh[:nb]); keep(cb, dbh[nb:nb + nc])
+            if vb:
+                g["value_head.linear.bias"] = dbh[nb + nc:nh].clone()
+        if dwh is not None:
+            keep(bw, dwh[:nb]); keep(cw, dwh[nb:nb + nc])
+            if vw:
+                g["value_head.linear.weight"] = dwh[nb + nc:nh].clone()
         del dz, dwh
+        if not below:
+            return g, None
         # final_ln
-        g["net.final_ln.weight"], g["net.final_ln.bias"] = zeros(hid), zeros(hid)
-        dx = ops.layernorm_backward(S["y"] if self.has_lastlayer else x_trunk, P["net.final_ln.weight"], dlat, g["net.final_ln.weight"],
-                                    g["net.final_ln.bias"], relu_in=self.final_ln_relu)
+        dx = layernorm_backward(S["y"] if self.has_lastlayer else x_trunk, "net.final_ln.", dlat, relu_in=self.final_ln_relu)
         del dlat
+        if cut >= 3 + n_layers:
+            return g, None
         if self.has_lastlayer:      # y = relu(xb Wl^T); gate dy by y > 0 while casting to the GEMM operand
+            below = cut < 2 + n_layers
+            lw = "net.lastlayer.layer.weight"
+            go_on = below or any_of("net.lastlayer.norm.weight", "net.lastlayer.norm.bias")
             dy = dx
             dy16 = ops.gate_cast(dy, hid, mask=S["y16"])
-            dxb, _, g["net.lastlayer.layer.weight"] = linear_backward(dy16, hid, S["xb"], P["net.lastlayer.layer.weight"])
-            g["net.lastlayer.norm.weight"], g["net.lastlayer.norm.bias"] = zeros(hid), zeros(hid)
-            dx = ops.layernorm_backward(x_trunk, P["net.lastlayer.norm.weight"], dxb, g["net.lastlayer.norm.weight"],
-                                        g["net.lastlayer.norm.bias"], relu_in=True)
+            dxb, _, dw = linear_backward(dy16, hid, S["xb"], P[lw], need_dx=go_on, need_dw=want(lw))
+            keep(lw, dw)
+            if not go_on:
+                return g, None
+            dx = layernorm_backward(x_trunk, "net.lastlayer.norm.", dxb, relu_in=True)
             if debug is not None:
                 debug['y'] = S["y"].clone(); debug['dy'] = dy.clone(); debug['dx_trunk'] = dx.clone(); debug['x_trunk'] = x_trunk.clone()
-            del dy, dy16, dxb
+            del dy, dy16, dxb, dw
+            if not below:
+                return g, None
         # transformer blocks, last to first
-        for l in reversed(range(cfg["n_layers"])):
+        for l in reversed(range(n_layers)):
             p = f"net.recurrent_layer.blocks.{l}."
             o = p + "r.orc_block."
             s = saved[l]
+            below = cut < 2 + l
+            # the block's tensors in the order the walk meets them; ahead(k): something trainable is left after stage k (or below the block)
+            stages = () if below else (
+                [p + "mlp1.layer.weight", p + "mlp1.layer.bias"], [p + "mlp0.layer.weight"], [p + "mlp0.norm.weight", p + "mlp0.norm.bias"],
+                [o + "proj_layer.weight", o + "proj_layer.bias"], [o + "b_nd"],
+                [f"{o}{c}_layer.weight" for c in "qkvr"] + [o + "q_layer.bias", o + "r_layer.bias"], [p + "pre_r_ln.weight", p + "pre_r_ln.bias"])
+            ahead = lambda k: below or any(any_of(*names) for names in stages[k + 1:])
             dout16 = ops.gate_cast(dx, hid, dtype=self.dtype)
             # mlp1: out = x2 + h2 W1^T + b1
-            _, dh16, g[p + "mlp1.layer.weight"] = linear_backward(dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"],
-                                                                  dx_f32=False, dx_bf16_ld=hid * ratio)
-            g[p + "mlp1.layer.bias"] = zeros(hid)
-            ops.column_sum_(g[p + "mlp1.layer.bias"], dout16, hid)
+            _, dh16, dw = linear_backward(dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"], dx_f32=False, dx_bf16_ld=hid * ratio,
+                                          need_dx=ahead(0), need_dw=want(p + "mlp1.layer.weight"))
+            keep(p + "mlp1.layer.weight", dw)
+            if want(p + "mlp1.layer.bias"):
+                g[p + "mlp1.layer.bias"] = zeros(hid)
+                ops.column_sum_(g[p + "mlp1.layer.bias"], dout16, hid)
+            if not ahead(0):
+                return g, None
             # mlp0: h2 = relu(hb W0^T)  (the ReLU gate was applied by the mask above)
-            dhb, _, g[p + "mlp0.layer.weight"] = linear_backward(dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"])
-            g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"] = zeros(hid), zeros(hid)
-            dx2 = ops.layernorm_backward(s["x2"], P[p + "mlp0.norm.weight"], dhb, g[p + "mlp0.norm.weight"], g[p + "mlp0.norm.bias"], dx_add=dx)
+            dhb, _, dw = linear_backward(dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"], need_dx=ahead(1), need_dw=want(p + "mlp0.layer.weight"))
+            keep(p + "mlp0.layer.weight", dw)
+            if not ahead(1):
+                return g, None
+            dx2 = layernorm_backward(s["x2"], p + "mlp0.norm.", dhb, dx_add=dx)
             if debug is not None:
                 debug[f'dout16_{l}'] = dout16.clone(); debug[f'dh16_{l}'] = dh16.clone(); debug[f'dhb_{l}'] = dhb.clone()
-            del dh16, dhb, dout16
+            del dh16, dhb, dout16, dw
+            if not ahead(2):
+                return g, None
             # proj: x2 = x1 + att Wp^T + bp
             dx2_16 = ops.gate_cast(dx2, hid, dtype=self.dtype)
-            datt, _, g[o + "proj_layer.weight"] = linear_backward(dx2_16, hid, s["att"], P[o + "proj_layer.weight"])
-            g[o + "proj_layer.bias"] = zeros(hid)
-            ops.column_sum_(g[o + "proj_layer.bias"], dx2_16, hid)
+            datt, _, dw = linear_backward(dx2_16, hid, s["att"], P[o + "proj_layer.weight"], need_dx=ahead(3), need_dw=want(o + "proj_layer.weight"))
+            keep(o + "proj_layer.weight", dw)
+            if want(o + "proj_layer.bias"):
+                g[o + "proj_layer.bias"] = zeros(hid)
+                ops.column_sum_(g[o + "proj_layer.bias"], dx2_16, hid)
+            if not ahead(3):
+                return g, None
             # attention, then the fused projection: dx1 = dx2 (skip) + dqkv Wqkv
             dqkv = self._attention_backward(S, l, datt, g)
+            if not want(o + "b_nd"):
+                g.pop(o + "b_nd", None)
+            if not ahead(4):
+                return g, None
             dq16 = ops.gate_cast(dqkv, _round_up(nq, 64), dtype=self.dtype)
             wq = torch.cat([P[f"{o}{c}_layer.weight"] for c in self.fused_qkv], 0)      # q_layer, k_layer, v_layer (, r_layer)
-            dx1, _, dwq = linear_backward(dq16, nq, s["x1b"], wq, res=dx2)
-            g[o + "q_layer.weight"], g[o + "k_layer.weight"], g[o + "v_layer.weight"] = dwq[:hid], dwq[hid:2 * hid], dwq[2 * hid:3 * hid]
+            dx1, _, dwq = linear_backward(dq16, nq, s["x1b"], wq, res=dx2, need_dx=ahead(5),
+                                          need_dw=any_of(*[f"{o}{c}_layer.weight" for c in self.fused_qkv]))
+            if dwq is not None:
+                keep(o + "q_layer.weight", dwq[:hid]); keep(o + "k_layer.weight", dwq[hid:2 * hid]); keep(o + "v_layer.weight", dwq[2 * hid:3 * hid])
             # bias sums over the fused columns (k_layer and v_layer have none).  r_layer outside the fused projection is unreached: exact zeros
-            dbq = zeros(nq if r_fused else hid)
-            ops.column_sum_(dbq, dq16, dbq.numel())
-            g[o + "r_layer.weight"] = dwq[3 * hid:] if r_fused else torch.zeros_like(P[o + "r_layer.weight"])
-            g[o + "q_layer.bias"] = dbq[:hid]
-            g[o + "r_layer.bias"] = dbq[3 * hid:] if r_fused else torch.zeros_like(P[o + "r_layer.bias"])
-            g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"] = zeros(hid), zeros(hid)
-            dx = ops.layernorm_backward(s["x"], P[p + "pre_r_ln.weight"], dx1, g[p + "pre_r_ln.weight"], g[p + "pre_r_ln.bias"])
+            if r_fused:
+                if dwq is not None:
+                    keep(o + "r_layer.weight", dwq[3 * hid:])
+            else:
+                keep(o + "r_layer.weight", torch.zeros_like(P[o + "r_layer.weight"]) if want(o + "r_layer.weight") else None)
+                keep(o + "r_layer.bias", torch.zeros_like(P[o + "r_layer.bias"]) if want(o + "r_layer.bias") else None)
+            if any_of(o + "q_layer.bias", *([o + "r_layer.bias"] if r_fused else [])):
+                dbq = zeros(nq if r_fused else hid)
+                ops.column_sum_(dbq, dq16, dbq.numel())
+                keep(o + "q_layer.bias", dbq[:hid])
+                if r_fused:
+                    keep(o + "r_layer.bias", dbq[3 * hid:])
+            if not ahead(5):
+                return g, None
+            dx = layernorm_backward(s["x"], p + "pre_r_ln.", dx1)
             if debug is not None:
                 debug[f'dx_block{l}'] = dx.clone(); debug[f'dx2_block{l}'] = dx2.clone(); debug[f'datt{l}'] = datt.clone(); debug[f'dqkvr{l}'] = dqkv.clone()
                 debug[f'dx1_block{l}'] = dx1.clone(); debug[f'dq16_{l}'] = dq16.clone(); debug[f'dx2_16_{l}'] = dx2_16.clone()
             del dx2, dx2_16, datt, dqkv, dq16, dx1, dwq
+            if not below:
+                return g, None
         if cfg["use_pre_lstm_ln"]:
-            g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"] = zeros(hid), zeros(hid)
-            dx = ops.layernorm_backward(S["x_pre"], P["net.pre_lstm_ln.weight"], dx, g["net.pre_lstm_ln.weight"], g["net.pre_lstm_ln.bias"])
+            dx = layernorm_backward(S["x_pre"], "net.pre_lstm_ln.", dx)
+            if cut >= 1:
+                return g, None
         # ImgObsProcess.linear: x = relu(dn Wlin^T); its LayerNorm sits on relu(d), d being the CNN's output
+        go_on = cut < 0 or any_of(pl + "norm.weight", pl + "norm.bias")
         dx16 = ops.gate_cast(dx, hid, mask=S["x_lin16"])
-        ddn, _, g[pl + "layer.weight"] = linear_backward(dx16, hid, S["dn"], P[pl + "layer.weight"])
-        g[pl + "norm.weight"], g[pl + "norm.bias"] = zeros(256), zeros(256)
-        dd = ops.layernorm_backward(S["d"], P[pl + "norm.weight"], ddn, g[pl + "norm.weight"], g[pl + "norm.bias"], relu_in=True)
+        ddn, _, dw = linear_backward(dx16, hid, S["dn"], P[pl + "layer.weight"], need_dx=go_on, need_dw=want(pl + "layer.weight"))
+        keep(pl + "layer.weight", dw)
+        if not go_on:
+            return g, None
+        dd = layernorm_backward(S["d"], pl + "norm.", ddn, relu_in=True)
         return g, dd

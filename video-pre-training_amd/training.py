@@ -34,8 +34,14 @@ from .trainer_base import TrainerBase, _round_up, linear_backward  # noqa: F401 
 class BCTrainer(TrainerBase):
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  train_cnn: bool = True, optimizer_state: bool = True, loss_scale: Optional[float] = None,
-                 scale_growth_interval: int = 200, episode_starts: str = "chunk", max_grad_norm: Optional[float] = None):
-        """max_grad_norm: None (default: no clipping -- the reference's actual behaviour, its clip_grad_norm_ call receives an exhausted generator),
+                 scale_growth_interval: int = 200, episode_starts: str = "chunk", max_grad_norm: Optional[float] = None,
+                 trainable=None, param_groups=None, decoupled_weight_decay: bool = False):
+        """trainable / param_groups / decoupled_weight_decay: partial fine-tuning (TrainerBase._init_trainer): which tensors train --
+        None = all this trainer trains, or parameter names / module prefixes such as ["pi_head", "net.lastlayer"], or a callable; selecting
+        `value_head.*`, or `net.img_process.cnn.*` with train_cnn=False, raises ValueError --, per-group lr_scale / weight_decay, AdamW-style decay.
+        The backward stops where training stops; with any CNN tensor trainable the whole CNN backward runs (no cut inside the CNN) and the frozen
+        CNN tensors are dropped from the gradients.
+        max_grad_norm: None (default: no clipping -- the reference's actual behaviour, its clip_grad_norm_ call receives an exhausted generator),
         5.0 (MAX_GRAD_NORM, what behavioural_cloning.py:38-40,121 meant) or float("inf") (measure the norm, never clip).  When set, step() takes the
         global l2 norm of the gradients of the mean loss on the device -- after the all-reduce, un-scaled: neither fp16's loss scale nor 1 / frames
         reaches the threshold -- and the Adam launch multiplies by torch's clip coefficient; `metrics` gains grad_norm, clip_coef and
@@ -55,7 +61,8 @@ class BCTrainer(TrainerBase):
         1 / (loss_scale x global_frames).  `loss_scale` (default 256 for fp16, 1 = off for bf16) is dynamic as in
         torch.cuda.amp.GradScaler: vpt_grads_nonfinite_multi checks the (all-reduced) gradients; an overflowed step is skipped on
         the device (the Adam launch reads the flag) and the scale halves, it doubles after `scale_growth_interval` clean steps."""
-        self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm)
+        self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
+                           trainable, param_groups, decoupled_weight_decay)
         self.episode_starts = check_episode_starts(episode_starts)
         # the autograd boundary's counterpart of loss_scale (lib/policy.py:_PolicyForwardFn.backward): where the largest incoming
         # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow it detects
@@ -175,7 +182,9 @@ class BCTrainer(TrainerBase):
             with (torch.cuda.stream(streams[ci % len(streams)]) if streams else contextlib.nullcontext()):
                 if self.train_cnn:
                     xn, sv = self._cnn_forward_saving(frames[i:i + eng.cnn_chunk])
-                    cnn_saved.append(sv)
+                    if self._cnn_backward:       # (a subset without a CNN tensor: the same forward, nothing of it kept)
+                        cnn_saved.append(sv)
+                    del sv
                 else:
                     xn = eng._cnn_chunk(frames[i:i + eng.cnn_chunk])
                 d32, _ = ops.linear(xn.view(xn.shape[0], -1), w["net.img_process.cnn.dense.w"], 256, splitk=DENSE_SPLITK)
@@ -208,8 +217,8 @@ class BCTrainer(TrainerBase):
               for h, n_ in (("buttons", nb), ("camera", nc))}
         lp_b = ops.log_softmax_cols(logits, 0, nb, temp, mask=mk["buttons"])
         lp_c = ops.log_softmax_cols(logits, nb, nc, temp, mask=mk["camera"])
-        return dict(trunk, m=m, bsz=bsz, t=t, dev=dev, d=d, xb=xb, y=y, y16=y16, lb=lb, logits=logits, lp_b=lp_b, lp_c=lp_c,
-                    cnn_saved=cnn_saved, state_out=state_out, ldz=_round_up(nb + nc + 1, 64), mask=mk)
+        return self._release_unread(dict(trunk, m=m, bsz=bsz, t=t, dev=dev, d=d, xb=xb, y=y, y16=y16, lb=lb, logits=logits, lp_b=lp_b, lp_c=lp_c,
+                                         cnn_saved=cnn_saved, state_out=state_out, ldz=_round_up(nb + nc + 1, 64), mask=mk))
 
     def _attention_backward(self, S, l, datt, g):
         """The masked attention's backward; the relative-position bias b_nd is trained by it."""
@@ -224,13 +233,14 @@ class BCTrainer(TrainerBase):
     def backward_from(self, S: dict, dz: torch.Tensor, on_trunk_grads=None, debug: Optional[dict] = None, value_grads: bool = False):
         """Backward of everything below the head logits.  dz: bf16 [M, ldz] = d loss / d (fused head logits).
         Consumes S (the CNN activations are released chunk by chunk).  value_grads: also return the value head's gradients
-        (non-zero only when dz's value column is)."""
+        (non-zero only when dz's value column is).  With a trainable subset the trunk's walk stops at its cut (TrainerBase._trunk_backward); the CNN
+        is not cut: when one of its tensors is trainable its backward runs whole and the frozen CNN tensors' gradients are dropped at the end."""
         eng = self.engine
         P = {n: p.detach() for n, p in self.params.items()}
         g, dd = self._trunk_backward(S, dz, P, value_grads=value_grads, debug=debug)
         if on_trunk_grads is not None:
             on_trunk_grads(g)
-        if self.train_cnn:
+        if self.train_cnn and self._cnn_backward:
             m, cnn_saved = S["m"], S["cnn_saved"]
             acc = self._cnn_backward_begin(P)
             n_acc = max(1, min(self.cnn_streams, len(cnn_saved)))
@@ -244,6 +254,9 @@ class BCTrainer(TrainerBase):
                 main.wait_stream(st)
             self._cnn_backward_merge(accs)
             self._cnn_backward_finish(acc, P, g)
+            if self._subset is not None:
+                for n in [n for n in g if n.startswith("net.img_process.cnn.") and n not in self._subset]:
+                    del g[n]
         return g
 
     def _chunk_streams(self, n_chunks: int):
