@@ -251,6 +251,11 @@ int vpt_dense_fold_epilogue(const float* part, int splitk, const double* stats, 
 int vpt_linear_splitk_epilogue(const float* part, int splitk, const float* bias, const float* res, float* out_f32, void* out_bf16,
                                int M, int N, int ldr, int ldc, int ldcb, int relu, const void* mask, int ldm, void* stream);
 
+/* Merge of a low-rank adapter into an fp32 master weight: out[i][k] = W[i][k] + s * sum_j B[i][j] * A[j][k], W / out fp32 [n][K] (out may be W),
+ * A fp32 [r][K], B fp32 [n][r], 1 <= r <= 64.  fp32 throughout, j ascending, every multiply and every add rounded on its own (no contraction):
+ * acc = 0; acc = acc + B[i][j] * A[j][k]; out = W + s * acc -- a float32 restatement of these lines gives the same bits. */
+int vpt_lowrank_merge(const float* W, const float* A, const float* B, float* out, int n, int K, int r, float s, void* stream);
+
 /* Acting path (M = B*T <= 8 rows, K <= 3072; agent.py:190-206): nn.LayerNorm (optional ReLU on its input) FUSED into the linear
  * layer it feeds -- every LayerNorm of the policy does feed one (lib/xf.py:334-356 pre_r_ln -> q/k/v/r, ln -> mlp0; lib/util.py:58-82
  * FanInInitReLULayer(norm, linear); lib/policy.py:188,211-214 lastlayer, final_ln -> heads).  Same results, bit for bit, as

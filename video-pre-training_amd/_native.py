@@ -45,6 +45,7 @@ SIGNATURES = {
     "vpt_linear_wgrad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vpt_dense_fold_epilogue": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P],
     "vpt_linear_splitk_epilogue": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
+    "vpt_lowrank_merge": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
     "vpt_layernorm_forward": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vpt_masked_attention_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "vpt_kv_memory_update": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],

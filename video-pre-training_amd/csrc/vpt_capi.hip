@@ -428,6 +428,11 @@ int vpt_linear_splitk_epilogue(const float* part, int splitk, const float* bias,
   CHECK_LAUNCH(vpt_splitk_epilogue_launch(part, splitk, &a, (hipStream_t)stream), "vpt_linear_splitk_epilogue");
 }
 
+int vpt_lowrank_merge(const float* W, const float* A, const float* B, float* out, int n, int K, int r, float s, void* stream) {
+  if (r < 1 || r > 64) return fail(-1, "vpt_lowrank_merge: the rank must be in 1..64");
+  CHECK_LAUNCH(vpt_lowrank_merge_launch(W, A, B, out, n, K, r, s, (hipStream_t)stream), "vpt_lowrank_merge");
+}
+
 int vpt_layernorm_forward(const float* x, const float* gain, const float* bias, float* out_f32, void* out_bf16,
                           int M, int D, int relu_in, void* stream) {
   VptLayerNormArgs a = {};

@@ -582,6 +582,7 @@ int vpt_heads_bwd_launch(const VptHeadsBwdArgs* a, hipStream_t s);
 int vpt_grouped_lp_bwd_launch(const VptGroupedLpBwdArgs* a, hipStream_t s);
 int vpt_ln_bwd_launch(const VptLnBwdArgs* a, hipStream_t s);
 int vpt_gate_cast_launch(const VptGateCastArgs* a, hipStream_t s);
+int vpt_lowrank_merge_launch(const float* W, const float* A, const float* B, float* out, int n, int K, int r, float s, hipStream_t stream);   // vpt_lowrank.hip
 int vpt_colsum_launch(const VptColsumArgs* a, hipStream_t s);
 int vpt_clip_launch(const VptClipArgs* a, hipStream_t s);
 int vpt_augment_uniforms_launch(const int64_t* keys, float* out, long frames, uint64_t seed, uint32_t epoch, hipStream_t s);

@@ -46,8 +46,10 @@ class IDMTrainer(TrainerBase):
 
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  optimizer_state: bool = True, loss_scale: Optional[float] = None, scale_growth_interval: int = 200, train_cnn: bool = False,
-                 max_grad_norm: Optional[float] = None, trainable=None, param_groups=None, decoupled_weight_decay: bool = False):
-        """trainable / param_groups / decoupled_weight_decay: partial fine-tuning as BCTrainer's (TrainerBase._init_trainer); selecting
+                 max_grad_norm: Optional[float] = None, trainable=None, param_groups=None, decoupled_weight_decay: bool = False, adapters=None):
+        """adapters: an adapters.LowRankAdapters built on this IDM (DESIGN.md §20; r_layer sits outside its fused projection and is not adaptable);
+        trainable=None then means "no base tensor".
+        trainable / param_groups / decoupled_weight_decay: partial fine-tuning as BCTrainer's (TrainerBase._init_trainer); selecting
         what this trainer does not train -- `net.lastlayer.*` (unreached), the empty `b_nd`, the CNN side with train_cnn=False -- raises ValueError.
         With any tensor of the temporal conv or the CNN trainable their whole backward runs and the frozen ones are dropped from the gradients.
         max_grad_norm: global-norm gradient clipping as BCTrainer's (None = off, the default; float("inf") = measure only; a non-finite norm skips
@@ -66,7 +68,7 @@ class IDMTrainer(TrainerBase):
         defaults to 256 (1 = off in bf16), the loss gradient is written as loss_scale / temperature x (softmax - one-hot) per frame, the optimiser
         launch un-scales, an overflowed step is skipped on the device, the scale halves then and doubles after `scale_growth_interval` clean steps."""
         self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
-                           trainable, param_groups, decoupled_weight_decay)
+                           trainable, param_groups, decoupled_weight_decay, adapters)
         # the autograd boundary's counterpart of loss_scale (lib/policy.py:_IDMForwardFn.backward), as BCTrainer's: where the largest incoming
         # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow the boundary detects
         self.autograd_lift, self.autograd_overflows = 256.0, 0
@@ -252,9 +254,10 @@ class IDMTrainer(TrainerBase):
     def evaluate(self, img_u8, buttons, camera, *, frame_weight=None) -> dict:
         """Forward-only loss and metrics of a [B, T] chunk: IDMEngine.forward (nothing saved) + ops.idm_loss without dz."""
         ab, ac, w, _ = self._checked_inputs(img_u8, buttons, camera, frame_weight)
-        self.policy._ensure_packed()
         bsz, t = img_u8.shape[:2]
-        out = self.engine.forward(img_u8)
+        with self._adapters_applied():
+            self.policy._ensure_packed()
+            out = self.engine.forward(img_u8)
         (gb, nb), (gc, nc) = self.engine.button_shape, self.engine.camera_shape
         lp_b, lp_c = out["buttons"].reshape(bsz * t, gb, nb), out["camera"].reshape(bsz * t, gc, nc)
         _, frame_out, totals = ops.idm_loss(lp_b, lp_c, ab, ac, 0.0, weight=w, dtype=self.dtype, want_dz=False)

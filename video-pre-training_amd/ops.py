@@ -397,7 +397,7 @@ def _every_split_has_k_steps(k: int, sk: int) -> bool:
 
 
 def linear(a_bf16, wpk, n, bias=None, res=None, relu=False, out_f32=True, out_bf16=False, splitk=1, mask=None,
-           out_bf16_ld=None, splitk_raw=False, tiling="auto"):
+           out_bf16_ld=None, splitk_raw=False, tiling="auto", out=None, partials_extra=None):
     """a [M,K] bf16 (row stride = K) x packed weight -> ([M,n] fp32 or None, [M,ld] bf16 or None).
     mask: optional bf16 [M, >=n] gate (output zeroed where mask <= 0).  out_bf16_ld: row stride of the bf16
     output (>= n, extra columns zero) so it can feed the next GEMM as an A operand with K padded to 64.
@@ -405,7 +405,9 @@ def linear(a_bf16, wpk, n, bias=None, res=None, relu=False, out_f32=True, out_bf
     share the call), "latency" = the weight-streaming kernel (M <= 8: the acting step), "auto" = by M (vpt_linear_forward).
     splitk: an int (the caller's explicit factor: the dense layer), or "nk" = nk_splitk(n, k) finished by the epilogue kernel.  Under the
     named tilings ("throughput", "latency") the summation order over K is a function of (tiling, splitk, N, K) ONLY -- never of M:
-    the M-based automatic split below applies to tiling="auto" alone (the BC step's small test shapes)."""
+    the M-based automatic split below applies to tiling="auto" alone (the BC step's small test shapes).
+    out: an fp32 [M, n] buffer the unsplit product's fp32 result lands in (one slice of a partial-sum buffer).  partials_extra: linear_partials'
+    exit -- the kernel and the K split are decided HERE, for both."""
     _chk(a_bf16, OP16, "A"); _chk(wpk, OP16, "wpk"); _chk(bias, torch.float32, "bias")
     _chk(res, torch.float32, "res"); _chk(mask, OP16, "mask")
     m, k = a_bf16.shape
@@ -426,9 +428,19 @@ def linear(a_bf16, wpk, n, bias=None, res=None, relu=False, out_f32=True, out_bf
         tiles = ((m + 255) // 256) * ((n + 127) // 128)
         if tiles < 128:
             auto_sk = max(1, min(16, k // 512, 256 // tiles))
+    if out is not None:      # the fp32 result lands in the caller's [M, n] buffer (one slice of a partial-sum buffer: DESIGN.md section 20)
+        _chk(out, torch.float32, "out")
+        if tuple(out.shape) != (m, n) or not out_f32 or splitk != 1 or auto_sk != 1:
+            raise ValueError(f"linear(out=): an fp32 [{m}, {n}] buffer for an unsplit product with an fp32 result, got {tuple(out.shape)} (splitk {splitk}, automatic {auto_sk})")
     # the MFMA GEMM cuts K so that _every_split_has_k_steps tells whether every partial slice is written in full; the weight-streaming kernel cuts K its
     # own way (and a split without k-steps writes nothing): keep its zero-fill
     gemm = tl in (1, 4) or (tl == 0 and m > 8)
+    if partials_extra is not None:      # the raw slices of this call's own kernel and split, with room for the caller's: no epilogue stage runs
+        sk = max(int(splitk), auto_sk)
+        part = (torch.empty if gemm and _every_split_has_k_steps(k, sk) else torch.zeros)(sk + int(partials_extra), m, n, dtype=torch.float32, device=dev)
+        _call("vpt_linear_forward_tiled", dict(flops=2.0 * m * n * k, bytes=2.0 * (m * k + n * k) + 4.0 * m * n), ptr(a_bf16), ptr(wpk), None, None, ptr(part), None,
+              m, n, k, k, n, n, n, 0, sk, None, 0, tl, _stream(), fmt=fmt, label="vpt_linear_forward")
+        return part, sk
     partials = lambda sk: (torch.empty if gemm and _every_split_has_k_steps(k, sk) else torch.zeros)(sk, m, n, dtype=torch.float32, device=dev)
     o16 = None
     if out_bf16:
@@ -443,12 +455,55 @@ def linear(a_bf16, wpk, n, bias=None, res=None, relu=False, out_f32=True, out_bf
         return o32, o16
     o32 = None
     if out_f32:   # split-K: one [m, n] slice per split, summed below
-        o32 = partials(splitk) if splitk > 1 else torch.empty(m, n, dtype=torch.float32, device=dev)
+        o32 = partials(splitk) if splitk > 1 else (out if out is not None else torch.empty(m, n, dtype=torch.float32, device=dev))
     _call("vpt_linear_forward_tiled", dict(flops=2.0 * m * n * k, bytes=2.0 * (m * k + n * k) + 4.0 * m * n), ptr(a_bf16), ptr(wpk), ptr(bias), ptr(res), ptr(o32), ptr(o16),
           m, n, k, k, n, n, ld16, 1 if relu else 0, splitk, ptr(mask), mask.shape[1] if mask is not None else 0, tl, _stream(), fmt=fmt, label="vpt_linear_forward")
     if splitk > 1 and o32 is not None and not splitk_raw:
         o32 = o32.sum(0)           # fixed summation order: the result does not depend on scheduling
     return o32, o16                # (splitk_raw: the [splitk, M, n] partial slices, for an epilogue of the caller's)
+
+
+def linear_partials(a_bf16, wpk, n, extra=1, splitk=1, tiling="auto"):
+    """The raw fp32 partial slices of a [M, K] x packed weight, by the kernel and the K split ops.linear(a, wpk, n, splitk=, tiling=) takes for
+    the same arguments, in a buffer with room for `extra` more slices -> (part fp32 [S + extra, M, n], S).  Slices S .. are the caller's to fill
+    (ops.linear(out=part[S])); splitk_epilogue(part, ...) then sums all of them in order and applies the GEMM's epilogue.  With one extra slice
+    of exact zeros the result is ops.linear's own, bit for bit: the same accumulators, 0 + acc (+ 0), the same epilogue arithmetic."""
+    return linear(a_bf16, wpk, n, splitk=splitk, tiling=tiling, partials_extra=int(extra))
+
+
+def splitk_epilogue(part, bias=None, res=None, relu=False, out_f32=True, out_bf16=False, mask=None, out_bf16_ld=None, dtype=torch.bfloat16):
+    """part fp32 [S, M, n] -> epilogue(sum_s part[s]) (vpt_linear_splitk_epilogue): the slices summed in order from 0.f, then bias -> ReLU ->
+    gate `mask` -> + res, exactly ops.linear's options and outputs ([M, n] fp32 or None, [M, ld] 16-bit or None)."""
+    _chk(part, torch.float32, "part"); _chk(bias, torch.float32, "bias"); _chk(res, torch.float32, "res"); _chk(mask, OP16, "mask")
+    s_, m, n = part.shape
+    dt, fmt = _fmt(mask, dtype=None if mask is not None else dtype)
+    ld16 = (out_bf16_ld or n) if out_bf16 else n
+    o32 = torch.empty(m, n, dtype=torch.float32, device=part.device) if out_f32 else None
+    o16 = None
+    if out_bf16:
+        o16 = torch.zeros(m, ld16, dtype=dt, device=part.device) if ld16 > n else torch.empty(m, n, dtype=dt, device=part.device)
+    _call("vpt_linear_splitk_epilogue", dict(bytes=4.0 * (s_ + 1) * m * n), ptr(part), s_, ptr(bias), ptr(res), ptr(o32), ptr(o16),
+          m, n, n, n, ld16, 1 if relu else 0, ptr(mask), mask.shape[1] if mask is not None else 0, _stream(), fmt=fmt)
+    return o32, o16
+
+
+LOWRANK_MAX_RANK = 64
+
+
+def lowrank_merge(weight, a, b, s, out=None):
+    """out = weight + s * (b @ a) in fp32 with the rank index ascending and no contraction (vpt_lowrank_merge): weight fp32 [n, K], a fp32 [r, K],
+    b fp32 [n, r], 1 <= r <= 64; `out` may be `weight` (in place).  A float32 numpy restatement equals it bit for bit."""
+    _chk(weight, torch.float32, "weight"); _chk(a, torch.float32, "a"); _chk(b, torch.float32, "b"); _chk(out, torch.float32, "out")
+    n, k = weight.shape
+    r = a.shape[0]
+    if not 1 <= r <= LOWRANK_MAX_RANK or tuple(a.shape) != (r, k) or tuple(b.shape) != (n, r):
+        raise ValueError(f"lowrank_merge: weight [{n}, {k}] needs a [r, {k}] and b [{n}, r] with 1 <= r <= {LOWRANK_MAX_RANK}, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if out is None:
+        out = torch.empty_like(weight)
+    elif tuple(out.shape) != (n, k):
+        raise ValueError(f"lowrank_merge: out must be [{n}, {k}], got {tuple(out.shape)}")
+    _call("vpt_lowrank_merge", dict(flops=2.0 * n * k * r, bytes=8.0 * n * k), ptr(weight), ptr(a), ptr(b), ptr(out), n, k, r, ctypes.c_float(float(s)), _stream())
+    return out
 
 
 def linear_wgrad(dy16, x16, n, out=None):

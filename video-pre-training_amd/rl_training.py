@@ -226,11 +226,12 @@ class PPOTrainer(BCTrainer):
         """Forward-only loss and metrics of a [B, T] chunk -> (metrics dict as loss_and_grads fills it, state_out): the inference forward + ops.rl_loss
         without dz.  The value normaliser is NOT updated."""
         f = self._frame_inputs(img_u8, act_buttons, act_camera, old_log_prob, advantage, value_target, prior_lp, frame_weight)
-        self.policy._ensure_packed()
         eng = self.engine
         bsz, t = img_u8.shape[:2]
         m = bsz * t
-        out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
+        with self._adapters_applied():
+            self.policy._ensure_packed()
+            out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
         lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
         vnorm = self._value_norm(f["target"], f["w"], update=False)
         _, frame_out, totals = ops.rl_loss(lp_b, lp_c, f["ab"], f["ac"], f["old"], f["adv"], 0, 0.0, prior_buttons=f["qb"], prior_camera=f["qc"],
@@ -260,7 +261,8 @@ class PPOTrainer(BCTrainer):
         """pi_old of an auxiliary phase: the trainer's OWN policy through its inference forward (prior_logprobs applied to self.policy)
         -> (lp_buttons [M, nb], lp_camera [M, nc], state_out), fp32 (64 x 128 frames: 287 MB).  Taken once per phase, before the first aux_step; the
         tensors do not follow the weights afterwards.  Take it under the same logit masks as the steps that use it."""
-        return self.prior_logprobs(self.policy, img_u8, first, state_in)
+        with self._adapters_applied():      # (with adapters pi_old is base + adapters; prior_logprobs(self.policy, ...) alone is the frozen base)
+            return self.prior_logprobs(self.policy, img_u8, first, state_in)
 
     def _aux_inputs(self, img_u8, old_lp, value_target, frame_weight, global_weight=None):
         """Validation + flattening shared by aux_loss_and_grads and aux_evaluate -> dict of [M] / [M, n] device tensors, w / wsum."""
@@ -356,11 +358,12 @@ class PPOTrainer(BCTrainer):
         """Forward-only auxiliary loss and metrics of a [B, T] chunk -> (metrics dict as aux_loss_and_grads fills it, state_out): the inference
         forward + ops.ppg_aux_loss without dz.  The value normaliser is NOT updated."""
         f = self._aux_inputs(img_u8, old_lp, value_target, frame_weight)
-        self.policy._ensure_packed()
         eng = self.engine
         bsz, t = img_u8.shape[:2]
         m = bsz * t
-        out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
+        with self._adapters_applied():
+            self.policy._ensure_packed()
+            out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
         lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
         vnorm = self._value_norm(f["target"], f["w"], update=False)
         _, frame_out, totals = ops.ppg_aux_loss(lp_b, lp_c, f["ob"], f["oc"], 0, 0.0, value=out["vpred"].reshape(m), value_target=f["target"], vnorm=vnorm,

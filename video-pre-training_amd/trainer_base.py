@@ -11,7 +11,11 @@ The two trunks differ in five places, each a class attribute or a hook of Traine
 The CNN's part of either pass stays with cnn_training.CnnTrainingMixin and the trainers' own chunk loops.
 
 Partial fine-tuning lives here too: which tensors train (select_trainable, resolve_param_groups: host code on names), the trunk
-backward that stops at the first unit holding a trainable tensor, and the per-group Adam launch of the optimiser tail."""
+backward that stops at the first unit holding a trainable tensor, and the per-group Adam launch of the optimiser tail.
+
+So do low-rank adapters (adapters.LowRankAdapters): the adapted GEMMs (adapted_linear, adapted_linear_backward: base product + low-rank
+slice through the split-K epilogue), the stacked operands of the fused projection, and the places in the trunk's two passes that take them."""
+import contextlib
 from typing import Dict, List, Optional
 
 import torch
@@ -43,6 +47,70 @@ def linear_backward(dy16: torch.Tensor, n: int, x16: Optional[torch.Tensor], wei
     if need_dw:       # dW = dy^T x straight from the row-major activations (vpt_gemm_tn_kernel: LDS transpose reads, no copies)
         dw = ops.linear_wgrad(dy16, x16, np_)[:n]
     return dx32, dx16, dw
+
+
+# ---- low-rank adapters: the operands of one adapted GEMM, its forward and its backward, built from the existing kernels ----------
+def stack_operands(entries, n: int, k: int, device=None):
+    """entries: [(A fp32 [r_i, K], B fp32 [n_i, r_i], s_i, row0_i)] -- adapter i acts on output rows row0_i .. row0_i + n_i of an [n, K] weight ->
+    (a_stack fp32 [R, K]: the A's stacked, zero rows up to R = sum r_i rounded up to 64, the GEMM's K step; sb fp32 [n, R]: s_i B_i placed
+    block-diagonally, zeros elsewhere; spans [(row0_i, n_i, col0_i, r_i)]).  Then  sum_i s_i (x A_i^T) B_i^T  at its rows  ==  (x a_stack^T) sb^T.
+    s is applied HERE, on fp32, never to a 16-bit activation.  Plain torch on small tensors: runs on the CPU as well."""
+    rp = _round_up(sum(a.shape[0] for a, _, _, _ in entries), 64)
+    a_stack = torch.zeros(rp, k, dtype=torch.float32, device=device)
+    sb = torch.zeros(n, rp, dtype=torch.float32, device=device)
+    spans, c0 = [], 0
+    for a, b, s, row0 in entries:
+        r, ni = a.shape[0], b.shape[0]
+        a_stack[c0:c0 + r] = a
+        sb[row0:row0 + ni, c0:c0 + r] = b * s
+        spans.append((row0, ni, c0, r))
+        c0 += r
+    return a_stack, sb, spans
+
+
+def unstack_gradients(da_stack: torch.Tensor, db_stack: torch.Tensor, spans):
+    """The inverse on the gradients: da_stack [R, K] = d / d a_stack, db_stack [n, R] = dy^T u (d / d sb) -> [(dA_i [r_i, K], dy^T u's DIAGONAL
+    block [n_i, r_i])] -- dB_i is s_i times the latter; the off-diagonal blocks of a fused projection belong to no parameter and are dropped."""
+    return [(da_stack[c0:c0 + r], db_stack[row0:row0 + ni, c0:c0 + r]) for row0, ni, c0, r in spans]
+
+
+def adapted_linear(x16: torch.Tensor, wpk: torch.Tensor, n: int, a_stack: torch.Tensor, sb: torch.Tensor, bias=None, res=None, relu: bool = False,
+                   out_f32: bool = True, out_bf16: bool = False, mask=None, out_bf16_ld: Optional[int] = None, splitk=1, tiling: str = "auto"):
+    """y = epi(x W^T (+) u16 (sB)^T),  u16 = rnd16(x A^T)  -> (fp32 [M, n] or None, 16-bit or None, u16 [M, R]) with ops.linear's options.
+    Three GEMMs and the split-K epilogue: u16 (ops.linear, 16-bit output); the base product to raw fp32 slice(s), by the kernel and K split the
+    unadapted call takes (ops.linear_partials); the low-rank product into one more slice; vpt_linear_splitk_epilogue sums the slices in order and
+    applies bias -> ReLU -> gate -> + res.  With B = 0 the extra slice is exact zeros and the result is ops.linear's, bit for bit."""
+    dt = x16.dtype
+    rp = a_stack.shape[0]
+    _, u16 = ops.linear(x16, ops.pack_linear(a_stack, dtype=dt), rp, out_f32=False, out_bf16=True, splitk=splitk, tiling=tiling)
+    part, sk = ops.linear_partials(x16, wpk, n, extra=1, splitk=splitk, tiling=tiling)
+    ops.linear(u16, ops.pack_linear(sb, dtype=dt), n, out=part[sk], tiling=tiling)
+    o32, o16 = ops.splitk_epilogue(part, bias=bias, res=res, relu=relu, out_f32=out_f32, out_bf16=out_bf16, mask=mask, out_bf16_ld=out_bf16_ld, dtype=dt)
+    return o32, o16, u16
+
+
+def adapted_linear_backward(dy16: torch.Tensor, n: int, x16: torch.Tensor, weight: torch.Tensor, a_stack: torch.Tensor, sb: torch.Tensor,
+                            u16: torch.Tensor, need_dx: bool = True, res=None, mask=None, dx_f32: bool = True, dx_bf16_ld: Optional[int] = None,
+                            need_dw: bool = False):
+    """Backward of adapted_linear on the same kernels; arguments as linear_backward's + the forward's operands and its saved u16.
+    -> (dx fp32 or None, dx 16-bit or None, dW or None, da_stack fp32 [R, K], dy^T u16 fp32 [n, R]):
+        du16 = rnd16(dy (sB));   dx = epi(dy W (+) du16 A) with linear_backward's gate and skip;   d a_stack = du16^T x;   d sb = dy^T u16.
+    need_dw: the dense [n, K] wgrad GEMM as well -- a fused projection in which a layer WITHOUT an adapter trains; a frozen adapted weight
+    launches none."""
+    np_, k, rp, dt = dy16.shape[1], weight.shape[1], a_stack.shape[0], dy16.dtype
+    _, du16 = ops.linear(dy16, ops.pack_linear(sb, transposed=True, k_pad=np_, dtype=dt), rp, out_f32=False, out_bf16=True)
+    dx32 = dx16 = dw = None
+    if need_dx:
+        wt = ops.pack_linear(weight.contiguous(), transposed=True, k_pad=np_, dtype=dt)
+        part, sk = ops.linear_partials(dy16, wt, k, extra=1)
+        ops.linear(du16, ops.pack_linear(a_stack, transposed=True, k_pad=rp, dtype=dt), k, out=part[sk])
+        dx32, dx16 = ops.splitk_epilogue(part, res=res, mask=mask, out_f32=dx_f32, out_bf16=dx_bf16_ld is not None, out_bf16_ld=dx_bf16_ld, dtype=dt)
+        del wt, part
+    if need_dw:
+        dw = ops.linear_wgrad(dy16, x16, np_)[:n]
+    db_stack = ops.linear_wgrad(dy16, u16, np_)[:n]
+    da_stack = ops.linear_wgrad(du16, x16, rp)
+    return dx32, dx16, dw, da_stack, db_stack
 
 
 # ---- which tensors train (DESIGN.md §19): name selection and parameter groups, plain host code on names only ---------------------------------
@@ -134,9 +202,10 @@ class TrainerBase(CnnTrainingMixin):
     param_groups = ()            # the normalised groups of resolve_param_groups
     _group_of: Dict[str, int] = {}
     decoupled_weight_decay = False
+    adapters = None              # low-rank adapters (adapters.LowRankAdapters); None: the code path that has always run
 
     def _init_trainer(self, policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
-                      trainable=None, param_groups=None, decoupled_weight_decay=False):
+                      trainable=None, param_groups=None, decoupled_weight_decay=False, adapters=None):
         """The state every trainer keeps (the constructors' docstrings say what the arguments mean).
         trainable / param_groups / decoupled_weight_decay: partial fine-tuning, shared by the three trainers --
         trainable: None (default: the trainer's own rule, on the code path that has always run), an iterable of strings -- exact parameter names
@@ -148,7 +217,13 @@ class TrainerBase(CnnTrainingMixin):
         and no bias sum for a frozen tensor above it, and the saving forward keeps nothing the shortened backward does not read.  Inside the CNN
         nothing is cut: if any CNN tensor is trainable its whole backward runs and the frozen CNN tensors' gradients are dropped.
         param_groups: [dict(params=<strings as above>, lr_scale=1.0, weight_decay=<the trainer's>), ...]; lr_scale multiplies self.lr at step time.
-        decoupled_weight_decay: torch.optim.AdamW's decay instead of Adam's L2 term.  Either makes step() use ops.adam_step_groups_ (one launch)."""
+        decoupled_weight_decay: torch.optim.AdamW's decay instead of Adam's L2 term.  Either makes step() use ops.adam_step_groups_ (one launch).
+        adapters: an adapters.LowRankAdapters built on this policy.  Its `<module>.lora_A` / `.lora_B` tensors join self.params and
+        always train; trainable=None then means "no base tensor", strings (or a callable) add base tensors as above, and an adapted weight among
+        them is a ValueError (it is frozen under its adapter).  The moments, the norm and clip, the overflow check, micro-batches, loss scaling and
+        state_dict() run over adapters + selection through the same code; adapter names are selectable in param_groups; the cut is the lowest
+        level holding a trainable base tensor or an adapted module.  The saving forward and the backward take the adapted GEMMs (adapted_linear,
+        adapted_linear_backward) for adapted modules and the unchanged calls everywhere else."""
         self.train_cnn = bool(train_cnn)
         self.max_grad_norm = self._checked_max_grad_norm(max_grad_norm)
         self.policy = policy
@@ -162,8 +237,23 @@ class TrainerBase(CnnTrainingMixin):
         self._cnn_flags_from_env()       # gated_dgrad, fused_pool, fold_n_backward, fold_n_backward0 (cnn_training.py)
         self.params: Dict[str, torch.nn.Parameter] = dict(policy.named_parameters())
         names = self._selectable_names()
-        self.trainable = select_trainable(list(self.params) if trainable is None else names, self._is_trainable, trainable, type(self).__name__)
-        if trainable is not None:
+        if adapters is None:
+            self.trainable = select_trainable(list(self.params) if trainable is None else names, self._is_trainable, trainable, type(self).__name__)
+        else:
+            who = type(self).__name__
+            if getattr(adapters, "_policy_id", None) != id(policy):
+                raise ValueError(f"{who}(adapters=): these adapters were built on another policy object")
+            if adapters.fused != self.fused_qkv:
+                raise ValueError(f"{who}(adapters=): the adapters were resolved for a fused {adapters.fused!r} projection, this trainer runs {self.fused_qkv!r}")
+            base = [] if trainable is None else select_trainable(names, self._is_trainable, trainable, who)
+            clash = sorted(set(base) & set(adapters.adapted_weights))
+            if clash:
+                raise ValueError(f"{who}(trainable=): {clash[:6]!r}{' ...' if len(clash) > 6 else ''} are frozen under an adapter; train the adapter or the weight, not both")
+            self.adapters = adapters
+            self.params.update(adapters.params)      # the same tensor objects: the Adam launch updates the adapters in place
+            names = names + list(adapters.params)
+            self.trainable = base + list(adapters.params)
+        if trainable is not None or adapters is not None:
             self._subset = frozenset(self.trainable)
             self._cut = min(self._unit_level(n) for n in self.trainable)
             self._cnn_backward = self.train_cnn and self._cut < 0
@@ -188,7 +278,7 @@ class TrainerBase(CnnTrainingMixin):
         """The names a selector string is matched against: the parameters minus what no optimiser could ever move -- an empty tensor (the IDM's
         b_nd [10, 0]) and the value normaliser's statistics (Parameters only so that they travel with the state_dict; they move by update()).
         So "value_head" under PPOTrainer and a whole block under IDMTrainer select what there is to train instead of raising."""
-        return [n for n, p in self.params.items() if p.numel() and not n.startswith("value_head.normalizer.")]
+        return [n for n, p in self.params.items() if p.numel() and not n.startswith("value_head.normalizer.") and not n.endswith((".lora_A", ".lora_B"))]
 
     def _unit_level(self, name: str) -> int:
         """The trunk unit a parameter belongs to, in forward order: 0 net.img_process.linear, 1 net.pre_lstm_ln, 2 + l block l, 2 + n net.lastlayer,
@@ -242,7 +332,8 @@ class TrainerBase(CnnTrainingMixin):
         if set(sd["exp_avg"]) != set(self.m):
             raise KeyError(f"optimizer state does not match the trainable parameters: {sorted(set(sd['exp_avg']) ^ set(self.m))[:4]} ...")
         if "param_groups" in sd:            # (a dict without them leaves the constructor's groups and flag in place)
-            self.param_groups, self._group_of = resolve_param_groups(self._selectable_names(), self.trainable, sd["param_groups"], type(self).__name__)
+            self.param_groups, self._group_of = resolve_param_groups(self._selectable_names() + (list(self.adapters.params) if self.adapters is not None else []),
+                                                                          self.trainable, sd["param_groups"], type(self).__name__)
             self.decoupled_weight_decay = bool(sd.get("decoupled_weight_decay", False))
         self.step_count = int(sd["step"])
         self.lr, self.wd, self.betas, self.eps = sd["lr"], sd["weight_decay"], tuple(sd["betas"]), sd["eps"]
@@ -384,6 +475,7 @@ class TrainerBase(CnnTrainingMixin):
         multiplies by the clip coefficient on the device.  A non-finite norm skips the step on the device in BOTH formats (skipped_steps counts it;
         fp16 also halves its loss scale): torch.nn.utils.clip_grad_norm_ would instead write NaN into every parameter -- a deliberate difference.
         `metrics` (when given and max_grad_norm is set) gains grad_norm, clip_coef and grad_norm_per_tensor {name: norm}: device tensors."""
+        self._check_adapters_ready()
         names = [n for n in self.trainable if n in grads]
         clip = self.max_grad_norm is not None
         found_inf = torch.zeros(1, dtype=torch.int32, device=device) if (self.scaled or clip) else None
@@ -422,6 +514,34 @@ class TrainerBase(CnnTrainingMixin):
         self.policy._packed_key = None  # weights changed (in place, behind autograd's version counters): re-pack before the next forward
         return loss, False
 
+    # ---- low-rank adapters ---------------------------------------------------------------------------------------------
+    def _check_adapters_ready(self):
+        """Before a saving forward or an optimiser launch: merged adapters would be applied twice (the masters hold W + s B A), and the
+        data-parallel exchange does not carry adapter tensors."""
+        if self.adapters is None:
+            return
+        if self.adapters.merged:
+            raise RuntimeError(f"{type(self).__name__}: the adapters are merged into the policy (LowRankAdapters.merge_); unmerge_ before training")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(f"{type(self).__name__}(adapters=): data-parallel steps with adapters are not built "
+                                      "(torch.distributed is initialised with more than one rank)")
+
+    @contextlib.contextmanager
+    def _adapters_applied(self):
+        """For the forward-only paths (evaluate), which run the engine's inference forward on the packed policy weights: the adapters merged
+        into the masters for the duration (merge_ ... unmerge_, the masters restored bit for bit).  Nothing to do without adapters, or where the
+        caller has merged them already."""
+        ad = self.adapters
+        if ad is None or ad.merged:
+            yield
+            return
+        ad.merge_(self.policy)
+        try:
+            yield
+        finally:
+            ad.unmerge_(self.policy)
+
     # ---- the trunk: ImgObsProcess.linear, pre_lstm_ln, the transformer blocks ------------------------------------------------------------
     def _trunk_forward_saving(self, d: torch.Tensor, attend, **linear_kw) -> dict:
         """d fp32 [M, 256] (the dense layer's pre-ReLU output) -> dict(dn, x_lin16, x_pre, saved, x_trunk): S's entries for the trunk, `saved` holding
@@ -438,17 +558,32 @@ class TrainerBase(CnnTrainingMixin):
             x_pre = x
             x, _ = ops.layernorm(x_pre, w["prelstm.g"], w["prelstm.b"], out_f32=True, out_bf16=False, dtype=dt)
         saved: List[dict] = []
+        ad = self.adapters
+        self._check_adapters_ready()
+
+        def linear(key, blocks, x16, wpk, n, lo_saved, **kw):
+            """ops.linear, or -- where an adapter sits on one of the weight's row blocks [(module, rows)] -- adapted_linear, its
+            operands and u16 kept in lo_saved[key] for the backward.  Without adapters this IS the ops.linear call that has always run."""
+            lo = ad.operands(blocks, x16.shape[1]) if ad is not None else None
+            if lo is None:
+                return ops.linear(x16, wpk, n, **kw, **linear_kw)
+            o32, o16, u16 = adapted_linear(x16, wpk, n, lo[0], lo[1], **kw, **linear_kw)
+            lo_saved[key] = dict(a=lo[0], sb=lo[1], spans=lo[2], mods=lo[3], u16=u16)
+            return o32, o16
+
         for l in range(cfg["n_layers"]):
             p = f"net.recurrent_layer.blocks.{l}."
+            o = p + "r.orc_block."
+            los: dict = {}
             x1, x1b = ops.layernorm(x, w[p + "ln1.g"], w[p + "ln1.b"], out_f32=True, dtype=dt)
-            qkv, _ = ops.linear(x1b, w[p + fq + ".w"], eng.n_qkvr, bias=w[p + fq + ".b"], **linear_kw)
+            qkv, _ = linear("lo_qkv", [(f"{o}{c}_layer", hid) for c in fq], x1b, w[p + fq + ".w"], eng.n_qkvr, los, bias=w[p + fq + ".b"])
             att, own = attend(l, p, qkv)
-            x2, _ = ops.linear(att, w[p + "proj.w"], hid, bias=w[p + "proj.b"], res=x1, **linear_kw)      # x2 = x1 + proj (engine._block)
+            x2, _ = linear("lo_proj", [(o + "proj_layer", hid)], att, w[p + "proj.w"], hid, los, bias=w[p + "proj.b"], res=x1)      # x2 = x1 + proj (engine._block)
             _, hb = ops.layernorm(x2, w[p + "ln2.g"], w[p + "ln2.b"], dtype=dt)
-            _, h2 = ops.linear(hb, w[p + "mlp0.w"], hid * ratio, relu=True, out_f32=False, out_bf16=True, **linear_kw)
-            xo, _ = ops.linear(h2, w[p + "mlp1.w"], hid, bias=w[p + "mlp1.b"], res=x2, **linear_kw)
+            _, h2 = linear("lo_mlp0", [(p + "mlp0.layer", hid * ratio)], hb, w[p + "mlp0.w"], hid * ratio, los, relu=True, out_f32=False, out_bf16=True)
+            xo, _ = linear("lo_mlp1", [(p + "mlp1.layer", hid)], h2, w[p + "mlp1.w"], hid, los, bias=w[p + "mlp1.b"], res=x2)
             # a block below the cut is never walked by the backward: its activations go as the forward leaves them (None keeps the index)
-            saved.append(dict(own, x=x, x1b=x1b, att=att, x2=x2, hb=hb, h2=h2, **{fq: qkv}) if 2 + l >= self._cut else None)
+            saved.append(dict(own, x=x, x1b=x1b, att=att, x2=x2, hb=hb, h2=h2, **{fq: qkv}, **los) if 2 + l >= self._cut else None)
             x = xo
         if self._cut > 0:       # the backward stops above ImgObsProcess.linear (and, from 2 on, above pre_lstm_ln): their inputs are not read
             dn = x_lin16 = None
@@ -495,6 +630,19 @@ class TrainerBase(CnnTrainingMixin):
         def keep(name, tensor):
             if want(name):
                 g[name] = tensor
+
+        def backward_of(lo, dy16, n_, x16, weight, **kw):
+            """linear_backward, or -- lo: what the forward kept of an adapted GEMM -- adapted_linear_backward + the adapters' gradients into g:
+            dA_i = the rows of du16^T x, dB_i = s times the diagonal block of dy^T u16 (fp32 results)."""
+            if lo is None:
+                return linear_backward(dy16, n_, x16, weight, **kw)
+            dx32_, dx16_, dw_, da_stack, db_stack = adapted_linear_backward(dy16, n_, x16, weight, lo["a"], lo["sb"], lo["u16"], **kw)
+            for mod, (da, db) in zip(lo["mods"], unstack_gradients(da_stack, db_stack, lo["spans"])):
+                g[mod + ".lora_A"] = da.contiguous()
+                g[mod + ".lora_B"] = db * self.adapters.scale
+            return dx32_, dx16_, dw_
+
+        lora = (lambda *mods: [m_ + sfx for m_ in mods for sfx in (".lora_A", ".lora_B")]) if self.adapters is not None else (lambda *mods: [])
 
         def layernorm_backward(x, prefix, dy, **kw):      # prefix + "weight" / "bias"; a frozen LayerNorm's sums are computed and dropped
             dgain, dbias = zeros(x.shape[1]), zeros(x.shape[1])
@@ -557,14 +705,15 @@ class TrainerBase(CnnTrainingMixin):
             below = cut < 2 + l
             # the block's tensors in the order the walk meets them; ahead(k): something trainable is left after stage k (or below the block)
             stages = () if below else (
-                [p + "mlp1.layer.weight", p + "mlp1.layer.bias"], [p + "mlp0.layer.weight"], [p + "mlp0.norm.weight", p + "mlp0.norm.bias"],
-                [o + "proj_layer.weight", o + "proj_layer.bias"], [o + "b_nd"],
-                [f"{o}{c}_layer.weight" for c in "qkvr"] + [o + "q_layer.bias", o + "r_layer.bias"], [p + "pre_r_ln.weight", p + "pre_r_ln.bias"])
+                [p + "mlp1.layer.weight", p + "mlp1.layer.bias"] + lora(p + "mlp1.layer"), [p + "mlp0.layer.weight"] + lora(p + "mlp0.layer"),
+                [p + "mlp0.norm.weight", p + "mlp0.norm.bias"], [o + "proj_layer.weight", o + "proj_layer.bias"] + lora(o + "proj_layer"), [o + "b_nd"],
+                [f"{o}{c}_layer.weight" for c in "qkvr"] + [o + "q_layer.bias", o + "r_layer.bias"] + lora(*[f"{o}{c}_layer" for c in "qkvr"]),
+                [p + "pre_r_ln.weight", p + "pre_r_ln.bias"])
             ahead = lambda k: below or any(any_of(*names) for names in stages[k + 1:])
             dout16 = ops.gate_cast(dx, hid, dtype=self.dtype)
             # mlp1: out = x2 + h2 W1^T + b1
-            _, dh16, dw = linear_backward(dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"], dx_f32=False, dx_bf16_ld=hid * ratio,
-                                          need_dx=ahead(0), need_dw=want(p + "mlp1.layer.weight"))
+            _, dh16, dw = backward_of(s.get("lo_mlp1"), dout16, hid, s["h2"], P[p + "mlp1.layer.weight"], mask=s["h2"], dx_f32=False, dx_bf16_ld=hid * ratio,
+                                      need_dx=ahead(0), need_dw=want(p + "mlp1.layer.weight"))
             keep(p + "mlp1.layer.weight", dw)
             if want(p + "mlp1.layer.bias"):
                 g[p + "mlp1.layer.bias"] = zeros(hid)
@@ -572,7 +721,7 @@ class TrainerBase(CnnTrainingMixin):
             if not ahead(0):
                 return g, None
             # mlp0: h2 = relu(hb W0^T)  (the ReLU gate was applied by the mask above)
-            dhb, _, dw = linear_backward(dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"], need_dx=ahead(1), need_dw=want(p + "mlp0.layer.weight"))
+            dhb, _, dw = backward_of(s.get("lo_mlp0"), dh16, hid * ratio, s["hb"], P[p + "mlp0.layer.weight"], need_dx=ahead(1), need_dw=want(p + "mlp0.layer.weight"))
             keep(p + "mlp0.layer.weight", dw)
             if not ahead(1):
                 return g, None
@@ -584,7 +733,7 @@ class TrainerBase(CnnTrainingMixin):
                 return g, None
             # proj: x2 = x1 + att Wp^T + bp
             dx2_16 = ops.gate_cast(dx2, hid, dtype=self.dtype)
-            datt, _, dw = linear_backward(dx2_16, hid, s["att"], P[o + "proj_layer.weight"], need_dx=ahead(3), need_dw=want(o + "proj_layer.weight"))
+            datt, _, dw = backward_of(s.get("lo_proj"), dx2_16, hid, s["att"], P[o + "proj_layer.weight"], need_dx=ahead(3), need_dw=want(o + "proj_layer.weight"))
             keep(o + "proj_layer.weight", dw)
             if want(o + "proj_layer.bias"):
                 g[o + "proj_layer.bias"] = zeros(hid)
@@ -599,8 +748,8 @@ class TrainerBase(CnnTrainingMixin):
                 return g, None
             dq16 = ops.gate_cast(dqkv, _round_up(nq, 64), dtype=self.dtype)
             wq = torch.cat([P[f"{o}{c}_layer.weight"] for c in self.fused_qkv], 0)      # q_layer, k_layer, v_layer (, r_layer)
-            dx1, _, dwq = linear_backward(dq16, nq, s["x1b"], wq, res=dx2, need_dx=ahead(5),
-                                          need_dw=any_of(*[f"{o}{c}_layer.weight" for c in self.fused_qkv]))
+            dx1, _, dwq = backward_of(s.get("lo_qkv"), dq16, nq, s["x1b"], wq, res=dx2, need_dx=ahead(5),
+                                      need_dw=any_of(*[f"{o}{c}_layer.weight" for c in self.fused_qkv]))
             if dwq is not None:
                 keep(o + "q_layer.weight", dwq[:hid]); keep(o + "k_layer.weight", dwq[hid:2 * hid]); keep(o + "v_layer.weight", dwq[2 * hid:3 * hid])
             # bias sums over the fused columns (k_layer and v_layer have none).  r_layer outside the fused projection is unreached: exact zeros

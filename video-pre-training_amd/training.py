@@ -35,8 +35,10 @@ class BCTrainer(TrainerBase):
     def __init__(self, policy, lr: float = 0.000181, weight_decay: float = 0.039428, betas=(0.9, 0.999), eps: float = 1e-8,
                  train_cnn: bool = True, optimizer_state: bool = True, loss_scale: Optional[float] = None,
                  scale_growth_interval: int = 200, episode_starts: str = "chunk", max_grad_norm: Optional[float] = None,
-                 trainable=None, param_groups=None, decoupled_weight_decay: bool = False):
-        """trainable / param_groups / decoupled_weight_decay: partial fine-tuning (TrainerBase._init_trainer): which tensors train --
+                 trainable=None, param_groups=None, decoupled_weight_decay: bool = False, adapters=None):
+        """adapters: an adapters.LowRankAdapters built on this policy: its A / B tensors train on the frozen base; trainable=None then
+        means "no base tensor" and strings add base tensors; evaluate() sees base + adapters (merged for the call, restored bit for bit after it).
+        trainable / param_groups / decoupled_weight_decay: partial fine-tuning (TrainerBase._init_trainer): which tensors train --
         None = all this trainer trains, or parameter names / module prefixes such as ["pi_head", "net.lastlayer"], or a callable; selecting
         `value_head.*`, or `net.img_process.cnn.*` with train_cnn=False, raises ValueError --, per-group lr_scale / weight_decay, AdamW-style decay.
         The backward stops where training stops; with any CNN tensor trainable the whole CNN backward runs (no cut inside the CNN) and the frozen
@@ -62,7 +64,7 @@ class BCTrainer(TrainerBase):
         torch.cuda.amp.GradScaler: vpt_grads_nonfinite_multi checks the (all-reduced) gradients; an overflowed step is skipped on
         the device (the Adam launch reads the flag) and the scale halves, it doubles after `scale_growth_interval` clean steps."""
         self._init_trainer(policy, lr, weight_decay, betas, eps, train_cnn, optimizer_state, loss_scale, scale_growth_interval, max_grad_norm,
-                           trainable, param_groups, decoupled_weight_decay)
+                           trainable, param_groups, decoupled_weight_decay, adapters)
         self.episode_starts = check_episode_starts(episode_starts)
         # the autograd boundary's counterpart of loss_scale (lib/policy.py:_PolicyForwardFn.backward): where the largest incoming
         # gradient element is lifted to before it enters the 16-bit buffers; halved on every overflow it detects
@@ -148,11 +150,12 @@ class BCTrainer(TrainerBase):
             w, wsum = self._checked_weights(frame_weight, img_u8)
             if wsum == 0:
                 raise ValueError("frame_weight: every weight is zero (the loss sum w nll / sum w is undefined)")
-        self.policy._ensure_packed()
         eng = self.engine
         bsz, t = img_u8.shape[:2]
         m = bsz * t
-        out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
+        with self._adapters_applied():
+            self.policy._ensure_packed()
+            out = eng.forward(img_u8, first, state_in, episode_starts=self.episode_starts)
         lp_b, lp_c = out["buttons"].reshape(m, eng.n_buttons), out["camera"].reshape(m, eng.n_camera)
         ab = act_buttons.reshape(m).to(torch.int64).contiguous()
         ac = act_camera.reshape(m).to(torch.int64).contiguous()
