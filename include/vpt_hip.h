@@ -338,7 +338,10 @@ int vpt_log_softmax_forward(const float* logits, float* out, int M, int ld, int 
  *          rng_stream (Philox4x32-10: key = seed, counter = (element / 4, row, step, stream << 24), u = (word >> 8) * 2^-24 --
  *          what a captured acting step needs: a fresh draw per replay with no host generator in the loop).  The kernel does not
  *          advance `step`: vpt_act_epilogue does, once per acting step (or the host between calls).  noise and rng_state are
- *          mutually exclusive; both null = deterministic;
+ *          mutually exclusive; both null = deterministic.  The action is always in [0, n): a row on which no score compares greater
+ *          than the start value -- every score NaN (one NaN logit makes the whole row's log-probs NaN) or every score -inf (a noise
+ *          row of zeros) -- takes index 0, as torch.argmax does for an all-NaN and for an all--inf row; action_logp is then the
+ *          log-prob of index 0, NaN on a NaN row, which vpt_act_epilogue's nan_flag reports;
  *   action_logp [M] fp32, optional: log-prob of that action (CategoricalActionHead.logprob, lib/action_head.py:176-184). */
 int vpt_action_head_forward(const float* logits, const uint8_t* mask, const float* noise, const uint64_t* rng_state, uint32_t rng_stream,
                             float* out, int64_t* action, float* action_logp, int M, int ld, int col0, int n, float temperature, void* stream);

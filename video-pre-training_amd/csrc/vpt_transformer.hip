@@ -515,6 +515,10 @@ __global__ __launch_bounds__(64 * NW) void vpt_logsoftmax_kernel(VptLogSoftmaxAr
     if (tid == 0) {
       for (int k = 1; k < NW; ++k)
         if (red[2 * NW + k] > best || (red[2 * NW + k] == best && redi[k] < besti)) { best = red[2 * NW + k]; besti = redi[k]; }
+      // No score compared greater than the start value -- every score NaN (one NaN logit makes lse NaN) or -inf (a noise row of zeros) --
+      // and besti is still the sentinel: take index 0, torch.argmax's answer for an all-NaN and for an all--inf row.  Every read below
+      // stays inside the row; action_logp of a NaN row stays NaN (vpt_act_epilogue's flag reports it).
+      if (besti >= a.n) besti = 0;
       a.action[row] = besti;
       if (a.action_logp) a.action_logp[row] = ((mk && !mk[besti]) ? -100.0f : z[besti] / T) - lse;
     }
