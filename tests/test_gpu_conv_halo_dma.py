@@ -111,7 +111,7 @@ def test_odd_block_count_takes_the_kept_path(fmt):
             torch.cuda.synchronize()
     assert torch.equal(ys[0][0].view(torch.int16), ys[1][0].view(torch.int16)) and torch.equal(ys[0][1], ys[1][1])
     M16._check(c, fmt, ys[0][0], y64, rstd, f"conv3x3 cin 96 {fmt}")
-    M16._check_stats(ys[0][1], y64)
+    M16._check_stats(ys[0][1], ys[0][0], f"conv3x3 cin 96 {fmt}")
 
 
 @pytest.mark.parametrize("fmt", ["bf16", "fp16"])
