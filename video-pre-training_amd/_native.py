@@ -1,112 +1,88 @@
-"""ctypes binding of libvpt_hip.so (the C ABI declared in include/vpt_hip.h).
+"""ctypes binding of libvpt_hip.so, derived from the header that declares its C ABI.
+
+load() reads include/vpt_hip.h once per process and types EVERY function it declares (argtypes and restype) on both
+libraries: there is no second copy of a signature to keep in step.  The parser is strict -- a declaration it cannot read is
+an error that names it, never a skipped or guessed binding.  tests/golden/abi_signatures.json pins what was bound.
 
 The library is built in-tree by build.py.  There is NO fallback: if it cannot be loaded every op raises.
 """
+import collections
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_HEADER_PATH = os.path.join(_HERE, "..", "include", "vpt_hip.h")
 _LIB_PATH = os.environ.get("VPT_HIP_LIB") or os.path.join(_HERE, "libvpt_hip.so")   # VPT_HIP_LIB: profiling builds (tools/)
 # one library per 16-bit operand format (vpt_operand_format()): same sources, same ABI
 _LIB_PATHS = {"bf16": _LIB_PATH, "fp16": os.path.join(_HERE, "libvpt_hip_f16.so")}
 _libs = {}
+_header = None
 
-ABI_VERSION = 5      # VPT_HIP_ABI of the include/vpt_hip.h this signature table was written against
+ABI_VERSION = 5      # VPT_HIP_ABI of the include/vpt_hip.h that ops.py's positional call sites were written against
 
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_L = ctypes.c_long
-_D = ctypes.c_double
+# the scalar types a declaration may use (closed: anything else is an error); every `*` argument is a c_void_p
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+# identification: mandatory even in a VPT_HIP_LIB override build
+_IDENTIFICATION = ("vpt_version", "vpt_abi_version", "vpt_operand_format", "vpt_last_error")
 
-# name -> argtypes, exactly as declared in include/vpt_hip.h
-SIGNATURES = {
-    "vpt_conv_first_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_conv3d_t5_forward": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3d_t5_forward_indexed": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3d_t5_backward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_gather_rows": [_P, _P, _P, _L, _L, _I, _P],
-    "vpt_idm_decode": [_P] * 9 + [_L, _I, _D, _D, _D, _I, _P],
-    "vpt_pack_conv3x3": [_P, _P, _P, _P, _P, _P, _I, _I, _P],
-    "vpt_pack_linear": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_pack_conv_first": [_P, _P, _P, _I, _P],
-    "vpt_pack_conv3d_t5": [_P, _P, _P, _P, _I, _P],
-    "vpt_chw_to_blocked": [_P, _P, ctypes.c_int64, _I, _I, _I, _P],
-    "vpt_conv3x3_forward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_forward_tiled": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_pool_forward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_forward_folded": [_P] * 12 + [_I, _I, _I, _I, _I, _P],
-    "vpt_channel_stats": [_P, _P, _I, _I, _I, _P],
-    "vpt_nfold_coef": [_P] * 12 + [_I, _I, _I, _I, _P],
-    "vpt_maxpool_forward": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_frame_affine_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_linear_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "vpt_linear_forward_tiled": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
-    "vpt_linear_wgrad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_dense_fold_epilogue": [_P, _I, _P, _I, _P, _P, _P, _I, _I, _P],
-    "vpt_linear_splitk_epilogue": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "vpt_lowrank_merge": [_P, _P, _P, _P, _I, _I, _I, _F, _P],
-    "vpt_layernorm_forward": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vpt_masked_attention_forward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_kv_memory_update": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_log_softmax_forward": [_P, _P, _I, _I, _I, _I, _F, _P],
-    "vpt_action_head_forward": [_P, _P, _P, _P, ctypes.c_uint32, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "vpt_uniform_noise": [_P, ctypes.c_uint32, _P, _I, _I, _P],
-    "vpt_conv_backward_prepare": [_P] * 14 + [_I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_dgrad": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_pool_argmax_forward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_conv_backward_prepare_pooled": [_P] * 15 + [_I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_dgrad_gated": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv_backward_reduce": [_P] * 10 + [_I, _I, _I, _I, _I, _P],
-    "vpt_conv_first_backward": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_conv_first_backward_nfold": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_conv3x3_wgrad_scratch_floats": [_I, _I, _I],
-    "vpt_camera_discretize": [_P, _P, _L, _D, _D, _D, _I, _P],
-    "vpt_camera_undiscretize": [_P, _P, _L, _D, _D, _D, _I, _P],
-    "vpt_action_from_factored": [_P, _P, _P, _P, _L, _I, _P],
-    "vpt_action_to_factored": [_P, _P, _P, _P, _L, _I, _P],
-    "vpt_maxpool_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
-    "vpt_frame_affine_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_bc_nll_backward": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "vpt_bc_loss": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
-    "vpt_idm_loss": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
-    "vpt_rl_loss": [_P] * 9 + [ctypes.c_int64] + [_P] * 7 + [_I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P],
-    "vpt_ppg_aux_loss": [_P] * 5 + [ctypes.c_int64] + [_P] * 7 + [_I, _I, _I, _I, _F, _F, _F, _F, _P],
-    "vpt_gae": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P],
-    "vpt_rollout_record": [_P] * 6 + [ctypes.c_int64] * 4 + [_P] * 7 + [_I, _I, _I, ctypes.c_int64, _P],
-    "vpt_rollout_reward": [_P] * 7 + [_I, _I, _I, _P],
-    "vpt_full_attention_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_heads_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P],
-    "vpt_grouped_logprob_backward": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P],
-    "vpt_layernorm_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "vpt_gate_cast": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_column_sum": [_P, _P, _P, _I, _I, _I, _P],
-    "vpt_masked_attention_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_adam_step": [_P, _P, _P, _P, ctypes.c_uint64, _I, _F, _F, _F, _F, _F, _F, _P],
-    "vpt_adam_step_multi": [_P, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P],
-    "vpt_grads_nonfinite_multi": [_P, _I, _L, _P, _P],
-    "vpt_grad_norm_workspace_bytes": [_I, ctypes.c_int64],
-    "vpt_grad_norm_multi": [_P, _I, _L, _F, _F, _P, _P, _P, _P, _P],
-    "vpt_adam_step_multi_clip": [_P, _I, _L, _I, _F, _F, _F, _F, _F, _F, _P, _P, _P],
-    "vpt_grad_accumulate_multi": [_P, _I, _L, _P],
-    "vpt_adam_step_groups": [_P, _P, _I, _L, _I, _F, _F, _F, _F, _I, _P, _P, _P],
-    "vpt_layernorm_linear_forward": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_masked_attention_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_masked_attention_step_inplace": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "vpt_act_epilogue": [_P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _I, _P],
-    "vpt_clip_frames": [_P, _I, _I, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P],
-    "vpt_augment_uniforms": [_P, _P, _L, ctypes.c_uint64, ctypes.c_uint32, _P],
-    "vpt_augment_frames": [_P, _P, _P, _L, _I, _I, _P],
-    "vpt_debug_poison_lds": [_P],
-    "vpt_episode_bounds": [_P, _P, _P, _P, _I, _I, _I, _P],
-    "vpt_masked_attention_forward_episodes": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "vpt_masked_attention_backward_episodes": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-}
+Header = collections.namedtuple("Header", "abi functions workspace_ops")   # functions: name -> (restype, [argtypes]); workspace_ops: VPT_WS_* -> int
 
 
 class NativeLibraryError(RuntimeError):
     pass
+
+
+def parse_header(text: str) -> Header:
+    """The C ABI a header text declares: VPT_HIP_ABI, every `ret vpt_name(args);` and the VPT_WS_* enum."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    m = re.search(r"^[ \t]*#[ \t]*define[ \t]+VPT_HIP_ABI[ \t]+(\d+)[ \t]*$", text, flags=re.M)
+    if not m:
+        raise NativeLibraryError("the header does not define VPT_HIP_ABI")
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)                      # preprocessor lines
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    *statements, tail = text.split(";")
+    if tail.strip():
+        raise NativeLibraryError(f"cannot read the declaration `{' '.join(tail.split())}`: no terminating `;`")
+    functions, workspace_ops = {}, {}
+    for decl in (" ".join(s.split()) for s in statements):
+        enum = re.fullmatch(r"enum \{(.*)\}", decl)
+        if enum:
+            for item in enum.group(1).split(","):
+                m_item = re.fullmatch(r"\s*(VPT_WS_\w+) ?= ?(\d+)\s*", item)
+                if not m_item:
+                    raise NativeLibraryError(f"cannot read the enumerator `{item.strip()}` of `{decl}`")
+                workspace_ops[m_item.group(1)] = int(m_item.group(2))
+            continue
+        fn = re.fullmatch(r"(const char ?\*|\w+) ?(vpt_\w+) ?\(([^()]*)\)", decl)
+        if not fn:
+            raise NativeLibraryError(f"cannot read the declaration `{decl}`")
+        ret, name, args = fn.groups()
+        if name in functions:
+            raise NativeLibraryError(f"`{decl}` declares {name} a second time")
+        restype = ctypes.c_char_p if "*" in ret else _SCALARS.get(ret)
+        argtypes = []
+        for arg in ([] if args.strip() in ("", "void") else args.split(",")):
+            scalar = re.fullmatch(r"\s*(\w+) \w+\s*", arg)
+            argtypes.append(ctypes.c_void_p if "*" in arg else _SCALARS.get(scalar.group(1)) if scalar else None)
+        if restype is None or None in argtypes:
+            raise NativeLibraryError(f"cannot type the declaration `{decl}`: scalar types are {', '.join(_SCALARS)}")
+        functions[name] = (restype, argtypes)
+    return Header(int(m.group(1)), functions, workspace_ops)
+
+
+def header() -> Header:
+    """include/vpt_hip.h (it travels with the package tree), parsed once per process."""
+    global _header
+    if _header is None:
+        try:
+            with open(_HEADER_PATH) as f:
+                text = f.read()
+        except OSError as e:
+            raise NativeLibraryError(f"{_HEADER_PATH}: the header the binding is derived from cannot be read ({e})")
+        _header = parse_header(text)
+    return _header
 
 
 def lib_path():
@@ -124,6 +100,7 @@ def load(fmt: str = "bf16"):
     if not os.path.exists(path):
         raise NativeLibraryError(
             f"{path} is missing: run `python __graft_entry__.py` (build()) first; there is no CPU fallback")
+    hdr = header()
     lib = ctypes.CDLL(path)
     try:
         lib.vpt_abi_version.restype = ctypes.c_int
@@ -132,29 +109,19 @@ def load(fmt: str = "bf16"):
         abi = None
     if abi != ABI_VERSION:      # a stale .so would take a stream handle for a flag pointer, etc.: refuse before the first call
         raise NativeLibraryError(f"{path} has C-ABI version {abi}, this package binds version {ABI_VERSION}: rebuild it (`python __graft_entry__.py`)")
+    if hdr.abi != ABI_VERSION:
+        raise NativeLibraryError(f"{_HEADER_PATH} declares C-ABI version {hdr.abi}, this package binds version {ABI_VERSION}")
     override = fmt == "bf16" and bool(os.environ.get("VPT_HIP_LIB"))
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in hdr.functions.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:
             # only an A/B reference build named by VPT_HIP_LIB (tools/build_ref_lib.sh: an OLDER revision of the same ABI) may lack entry points
             # added since -- calling one raises below; the in-tree library must export every symbol
-            if override:
+            if override and name not in _IDENTIFICATION:
                 continue
             raise NativeLibraryError(f"{path} does not export {name}: rebuild it (`python __graft_entry__.py`)")
-        fn.argtypes = argtypes
-        fn.restype = _I
-    lib.vpt_version.restype = ctypes.c_char_p
-    lib.vpt_operand_format.restype = ctypes.c_char_p
-    lib.vpt_conv3x3_wgrad_scratch_floats.restype = ctypes.c_long
-    if hasattr(lib, "vpt_grad_norm_workspace_bytes"):
-        lib.vpt_grad_norm_workspace_bytes.restype = ctypes.c_long
-    lib.vpt_workspace_bytes.argtypes, lib.vpt_workspace_bytes.restype = [_I] * 6, ctypes.c_int64
-    lib.vpt_conv3x3_pool_seam_elems.argtypes, lib.vpt_conv3x3_pool_seam_elems.restype = [_I] * 4, ctypes.c_int64
-    for q, at in (("vpt_conv3x3_packed_elems", [_I, _I]), ("vpt_conv3x3_table_floats", [_I]), ("vpt_linear_packed_elems", [_I, _I]),
-                  ("vpt_conv_first_packed_elems", [_I]), ("vpt_conv3d_t5_packed_elems", [_I])):
-        getattr(lib, q).argtypes, getattr(lib, q).restype = at, ctypes.c_long
-    lib.vpt_last_error.restype = ctypes.c_char_p
+        fn.argtypes, fn.restype = argtypes, restype
     if lib.vpt_operand_format().decode() != fmt:
         raise NativeLibraryError(f"{path} reports operand format {lib.vpt_operand_format().decode()}, expected {fmt}")
     _libs[fmt] = lib

@@ -25,6 +25,44 @@ __global__ __launch_bounds__(256) void vpt_poison_lds_kernel(int words, unsigned
   for (int k = 0; k < 16; ++k) __builtin_amdgcn_s_sleep(127);
 }
 
+// ---- one builder per kernel argument block: zeroed, then the fields EVERY caller sets.  An entry point states only what makes it different. ----
+static VptConv3x3Args conv3x3_args(const void* x, const void* wpk, void* y, int frames, int H, int W, int Cin, int Cout) {
+  VptConv3x3Args a = {};
+  a.x = (const vpt_op16*)x; a.wpk = (const vpt_op16*)wpk; a.y = (vpt_op16*)y;
+  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.NT = (Cout + 127) / 128; a.CoutPad = a.NT * 128;
+  a.inv_count_in = 1.0 / ((double)Cin * H * W);
+  a.tiling = 1;
+  return a;
+}
+
+// (the sizes only: a caller assigns its many like-typed pointers by field name)
+static VptConvBwdPrepArgs conv_bwd_prep_args(int frames, int H, int W, int Cin, int Cout) {
+  VptConvBwdPrepArgs a = {};
+  a.frames = frames; a.CB = Cout / 32; a.H = H; a.W = W; a.CoutPad = ((Cout + 127) / 128) * 128;
+  a.inv_count_in = 1.0 / ((double)Cin * H * W);
+  return a;
+}
+
+static VptAttnArgs attn_args(const float* qkvr, const float* kmem, const float* vmem, const float* b_nd, void* out, int B, int t, int heads, int hid, int ld, int maxlen) {
+  VptAttnArgs a = {};
+  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.b_nd = b_nd; a.out = (vpt_op16*)out;
+  a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = 1;
+  return a;
+}
+
+static VptLogSoftmaxArgs log_softmax_args(const float* logits, float* out, int M, int ld, int col0, int n, float temperature) {
+  VptLogSoftmaxArgs a = {};
+  a.logits = logits; a.out = out; a.M = M; a.ld = ld; a.col0 = col0; a.n = n; a.temperature = temperature;
+  return a;
+}
+
+// Adam's bias corrections of step `step` (counted from 1), formed in double: step_size = lr / (1 - beta1^step), inv_sqrt_bc2 = 1 / sqrt(1 - beta2^step)
+static void adam_bias_terms(int step, float lr, float beta1, float beta2, VptAdamArgs* a) {
+  a->step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
+  a->inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+}
+
 extern "C" {
 
 const char* vpt_version(void) { return "vpt_hip 0.5 gfx950"; }
@@ -137,16 +175,9 @@ int vpt_conv3x3_forward_tiled(const void* x, const void* wpk, const float* edge_
                               int frames, int H, int W, int Cin, int Cout, int tiling, void* stream) {
   if (!stats_in) return fail(-1, "vpt_conv3x3_forward: stats_in is required");
   if (tiling < 1 || tiling > 3) return fail(-1, "vpt_conv3x3_forward_tiled: tiling must be 1 (throughput), 2 (latency) or 3 (throughput, 32-row tiles)");
-  VptConv3x3Args a = {};
-  a.gate_stats = nullptr; a.gate_u = nullptr; a.inv_count_gate = 0.0; a.pool_mask = nullptr;
+  VptConv3x3Args a = conv3x3_args(x, wpk, y, frames, H, W, Cin, Cout);
   a.tiling = tiling;
-  a.x = (const vpt_op16*)x; a.wpk = (const vpt_op16*)wpk; a.edge_sa = edge_sa; a.edge_sg = edge_sg;
-  a.stats_in = stats_in; a.res = (const vpt_op16*)res; a.y = (vpt_op16*)y; a.stats_out = stats_out;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.NT = (Cout + 127) / 128; a.CoutPad = a.NT * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.bwd = 0; a.xin = nullptr; a.coef = nullptr; a.pool = 0; a.seam_r = nullptr; a.seam_c = nullptr; a.out_gain = nullptr; a.chs_out = nullptr;
-  a.kk_frame = a.rs_frame = a.res_scale = a.res_bias = nullptr;
+  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.stats_in = stats_in; a.res = (const vpt_op16*)res; a.stats_out = stats_out;
   CHECK_LAUNCH(vpt_conv3x3_launch(&a, (hipStream_t)stream), "vpt_conv3x3_forward");
 }
 
@@ -157,15 +188,8 @@ int vpt_conv3x3_forward_folded(const void* x, const void* wpk, const float* edge
   if (!kk_frame && !stats_in) return fail(-1, "vpt_conv3x3_forward_folded: stats_in is required unless kk_frame replaces it");
   if (res_bias && (!res || !res_scale)) return fail(-1, "vpt_conv3x3_forward_folded: res_bias needs res and res_scale");
   if (!edge_sg || (!kk_frame && !edge_sa)) return fail(-1, "vpt_conv3x3_forward_folded: edge tables missing");
-  VptConv3x3Args a = {};
-  a.gate_stats = nullptr; a.gate_u = nullptr; a.inv_count_gate = 0.0; a.pool_mask = nullptr;
-  a.tiling = 1;
-  a.x = (const vpt_op16*)x; a.wpk = (const vpt_op16*)wpk; a.edge_sa = edge_sa; a.edge_sg = edge_sg;
-  a.stats_in = stats_in; a.res = (const vpt_op16*)res; a.y = (vpt_op16*)y; a.stats_out = stats_out;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.NT = (Cout + 127) / 128; a.CoutPad = a.NT * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.bwd = 0; a.xin = nullptr; a.coef = nullptr; a.pool = 0; a.seam_r = nullptr; a.seam_c = nullptr; a.out_gain = nullptr; a.chs_out = nullptr;
+  VptConv3x3Args a = conv3x3_args(x, wpk, y, frames, H, W, Cin, Cout);
+  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.stats_in = stats_in; a.res = (const vpt_op16*)res; a.stats_out = stats_out;
   a.kk_frame = kk_frame; a.rs_frame = rs_frame; a.res_scale = res_bias ? res_scale : nullptr; a.res_bias = res_bias;
   CHECK_LAUNCH(vpt_conv3x3_launch(&a, (hipStream_t)stream), "vpt_conv3x3_forward_folded");
 }
@@ -197,16 +221,9 @@ static int conv3x3_pool_forward_impl(const void* x, const void* wpk, const float
   if (!stats_in || !pooled || !seam_scratch) return fail(-1, "vpt_conv3x3_pool_forward: stats_in, pooled and seam_scratch are required");
   if (phases < 1 || phases > 3) return fail(-1, "vpt_conv3x3_pool_forward: phases = 1 (tiles), 2 (seams) or 3 (both)");
   if ((H & 15) || (W & 15) || (Cout & 31)) return fail(-1, "vpt_conv3x3_pool_forward: H, W multiples of 16, Cout of 32");
-  VptConv3x3Args a = {};
-  a.gate_stats = nullptr; a.gate_u = nullptr; a.inv_count_gate = 0.0; a.pool_mask = nullptr;
-  a.tiling = 1;
-  a.x = (const vpt_op16*)x; a.wpk = (const vpt_op16*)wpk; a.edge_sa = edge_sa; a.edge_sg = edge_sg;
-  a.stats_in = stats_in; a.res = nullptr; a.y = (vpt_op16*)pooled; a.stats_out = stats_out;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.NT = (Cout + 127) / 128; a.CoutPad = a.NT * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.bwd = 0; a.xin = nullptr; a.coef = nullptr; a.pool = 1; a.out_gain = out_gain; a.chs_out = chs_out; a.pool_mask = (vpt_op16*)pool_mask;
-  a.kk_frame = a.rs_frame = a.res_scale = a.res_bias = nullptr;
+  VptConv3x3Args a = conv3x3_args(x, wpk, pooled, frames, H, W, Cin, Cout);
+  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.stats_in = stats_in; a.stats_out = stats_out;
+  a.pool = 1; a.out_gain = out_gain; a.chs_out = chs_out; a.pool_mask = (vpt_op16*)pool_mask;
   a.seam_r = (vpt_op16*)seam_scratch;
   a.seam_c = a.seam_r + (size_t)frames * Cout * (H / 16) * W;
   if (phases & 1) {
@@ -234,27 +251,18 @@ int vpt_conv3x3_pool_argmax_forward(const void* x, const void* wpk, const float*
 
 int vpt_conv3x3_dgrad(const void* dacc, const void* wpk_t, const void* skip, const void* xin, const float* coef, void* dx,
                       int frames, int H, int W, int Cout, int Cin, void* stream) {
-  VptConv3x3Args a = {};
-  a.gate_stats = nullptr; a.gate_u = nullptr; a.inv_count_gate = 0.0; a.pool_mask = nullptr;
-  a.x = (const vpt_op16*)dacc; a.wpk = (const vpt_op16*)wpk_t; a.edge_sa = nullptr; a.edge_sg = nullptr;
-  a.stats_in = nullptr; a.res = (const vpt_op16*)skip; a.y = (vpt_op16*)dx; a.stats_out = nullptr;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cout; a.Cout = Cin;   // roles swap in the transposed convolution
-  a.NT = (Cin + 127) / 128; a.CoutPad = a.NT * 128; a.inv_count_in = 1.0;
-  a.bwd = 1; a.xin = (const vpt_op16*)xin; a.coef = coef; a.tiling = 1; a.pool = 0; a.seam_r = nullptr; a.seam_c = nullptr; a.out_gain = nullptr; a.chs_out = nullptr;
-  a.kk_frame = a.rs_frame = a.res_scale = a.res_bias = nullptr;
+  VptConv3x3Args a = conv3x3_args(dacc, wpk_t, dx, frames, H, W, /*Cin=*/Cout, /*Cout=*/Cin);   // roles swap in the transposed convolution
+  a.inv_count_in = 1.0;
+  a.bwd = 1; a.xin = (const vpt_op16*)xin; a.coef = coef; a.res = (const vpt_op16*)skip;
   CHECK_LAUNCH(vpt_conv3x3_launch(&a, (hipStream_t)stream), "vpt_conv3x3_dgrad");
 }
 
 int vpt_conv3x3_dgrad_gated(const void* dacc, const void* wpk_t, const void* xin, const float* coef, const double* gate_stats, int gate_cin,
                             void* dacc_out, double* gate_u, int frames, int H, int W, int Cout, int Cin, void* stream) {
   if (!gate_stats || !gate_u || gate_cin <= 0) return fail(-1, "vpt_conv3x3_dgrad_gated: gate_stats, gate_u and gate_cin are required");
-  VptConv3x3Args a = {};
-  a.x = (const vpt_op16*)dacc; a.wpk = (const vpt_op16*)wpk_t; a.edge_sa = nullptr; a.edge_sg = nullptr;
-  a.stats_in = nullptr; a.res = nullptr; a.y = (vpt_op16*)dacc_out; a.stats_out = nullptr;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cout; a.Cout = Cin;   // roles swap in the transposed convolution
-  a.NT = (Cin + 127) / 128; a.CoutPad = a.NT * 128; a.inv_count_in = 1.0;
-  a.bwd = 1; a.xin = (const vpt_op16*)xin; a.coef = coef; a.tiling = 1; a.pool = 0; a.seam_r = nullptr; a.seam_c = nullptr; a.out_gain = nullptr; a.chs_out = nullptr;
-  a.kk_frame = a.rs_frame = a.res_scale = a.res_bias = nullptr;
+  VptConv3x3Args a = conv3x3_args(dacc, wpk_t, dacc_out, frames, H, W, /*Cin=*/Cout, /*Cout=*/Cin);   // roles swap in the transposed convolution
+  a.inv_count_in = 1.0;
+  a.bwd = 1; a.xin = (const vpt_op16*)xin; a.coef = coef;
   a.gate_stats = gate_stats; a.gate_u = gate_u; a.inv_count_gate = 1.0 / ((double)gate_cin * H * W);
   CHECK_LAUNCH(vpt_conv3x3_launch(&a, (hipStream_t)stream), "vpt_conv3x3_dgrad_gated");
 }
@@ -263,13 +271,9 @@ int vpt_conv_backward_reduce(const void* dacc, const double* gate_u, const doubl
                              double* t12, float* coef, float* d_sa, float* d_sg, float* scratch, int frames, int H, int W, int Cin, int Cout, void* stream) {
   if (Cout & 31) return fail(-1, "vpt_conv_backward_reduce: Cout must be a multiple of 32");
   if (!dacc || !gate_u) return fail(-1, "vpt_conv_backward_reduce: dacc and gate_u are required");
-  VptConvBwdPrepArgs a = {};
-  a.dpooled = nullptr; a.argmax = nullptr; a.sbuf = scratch; a.wshift = 0; a.coef = coef;
-  a.dy = (const vpt_op16*)dacc; a.y = nullptr; a.res = nullptr; a.stats_in = stats_in;
-  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.dacc = nullptr; a.t12 = t12; a.d_sa = d_sa; a.d_sg = d_sg;
-  a.frames = frames; a.CB = Cout / 32; a.H = H; a.W = W; a.CoutPad = ((Cout + 127) / 128) * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.gate_u = gate_u; a.pooled = nullptr; a.pool_mask = nullptr;
+  VptConvBwdPrepArgs a = conv_bwd_prep_args(frames, H, W, Cin, Cout);
+  a.stats_in = stats_in; a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.t12 = t12; a.coef = coef; a.d_sa = d_sa; a.d_sg = d_sg; a.sbuf = scratch;
+  a.dy = (const vpt_op16*)dacc; a.gate_u = gate_u;
   CHECK_LAUNCH(vpt_conv_bwd_prep_launch(&a, (hipStream_t)stream), "vpt_conv_backward_reduce");
 }
 
@@ -278,13 +282,9 @@ int vpt_conv_backward_prepare_pooled(const void* dpooled, const void* pooled, co
                                      const float* n_gain, const double* pool_stats, const double* pool_ab, int frames, int H, int W, int Cin, int Cout, void* stream) {
   if (Cout & 31) return fail(-1, "vpt_conv_backward_prepare_pooled: Cout must be a multiple of 32");
   if (!dpooled || !pooled || !pool_mask || !dacc) return fail(-1, "vpt_conv_backward_prepare_pooled: dpooled, pooled, pool_mask and dacc are required");
-  VptConvBwdPrepArgs a = {};
-  a.dpooled = (const vpt_op16*)dpooled; a.argmax = nullptr; a.sbuf = scratch; a.wshift = 0; a.coef = coef;
-  a.dy = nullptr; a.y = nullptr; a.res = nullptr; a.stats_in = stats_in;
-  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.dacc = (vpt_op16*)dacc; a.t12 = t12; a.d_sa = d_sa; a.d_sg = d_sg;
-  a.frames = frames; a.CB = Cout / 32; a.H = H; a.W = W; a.CoutPad = ((Cout + 127) / 128) * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.gate_u = nullptr; a.pooled = (const vpt_op16*)pooled; a.pool_mask = (const vpt_op16*)pool_mask;
+  VptConvBwdPrepArgs a = conv_bwd_prep_args(frames, H, W, Cin, Cout);
+  a.stats_in = stats_in; a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.t12 = t12; a.coef = coef; a.d_sa = d_sa; a.d_sg = d_sg; a.sbuf = scratch;
+  a.dpooled = (const vpt_op16*)dpooled; a.dacc = (vpt_op16*)dacc; a.pooled = (const vpt_op16*)pooled; a.pool_mask = (const vpt_op16*)pool_mask;
   a.n_gain = n_gain; a.pool_stats = pool_stats; a.pool_ab = pool_ab; a.inv_count_pool = 1.0 / ((double)Cout * (H / 2) * (W / 2));
   CHECK_LAUNCH(vpt_conv_bwd_prep_launch(&a, (hipStream_t)stream), "vpt_conv_backward_prepare_pooled");
 }
@@ -293,13 +293,9 @@ int vpt_conv_backward_prepare(const void* dy, const void* dpooled, const uint8_t
                               const double* stats_in, const float* edge_sa, const float* edge_sg, void* dacc, double* t12,
                               float* coef, float* d_sa, float* d_sg, float* scratch, int frames, int H, int W, int Cin, int Cout, void* stream) {
   if (Cout & 31) return fail(-1, "vpt_conv_backward_prepare: Cout must be a multiple of 32");
-  VptConvBwdPrepArgs a = {};
-  a.dpooled = (const vpt_op16*)dpooled; a.argmax = argmax; a.sbuf = scratch; a.wshift = 0; a.coef = coef;
-  a.dy = (const vpt_op16*)dy; a.y = (const vpt_op16*)y; a.res = (const vpt_op16*)res; a.stats_in = stats_in;
-  a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.dacc = (vpt_op16*)dacc; a.t12 = t12; a.d_sa = d_sa; a.d_sg = d_sg;
-  a.frames = frames; a.CB = Cout / 32; a.H = H; a.W = W; a.CoutPad = ((Cout + 127) / 128) * 128;
-  a.inv_count_in = 1.0 / ((double)Cin * H * W);
-  a.gate_u = nullptr; a.pooled = nullptr; a.pool_mask = nullptr;
+  VptConvBwdPrepArgs a = conv_bwd_prep_args(frames, H, W, Cin, Cout);
+  a.stats_in = stats_in; a.edge_sa = edge_sa; a.edge_sg = edge_sg; a.t12 = t12; a.coef = coef; a.d_sa = d_sa; a.d_sg = d_sg; a.sbuf = scratch;
+  a.dy = (const vpt_op16*)dy; a.dpooled = (const vpt_op16*)dpooled; a.argmax = argmax; a.y = (const vpt_op16*)y; a.res = (const vpt_op16*)res; a.dacc = (vpt_op16*)dacc;
   CHECK_LAUNCH(vpt_conv_bwd_prep_launch(&a, (hipStream_t)stream), "vpt_conv_backward_prepare");
 }
 
@@ -329,7 +325,7 @@ long vpt_conv3x3_wgrad_scratch_floats(int frames, int Cin, int Cout) {
 int vpt_conv3x3_wgrad(const void* dacc, const void* x, float* dw, float* scratch, int frames, int H, int W, int Cin, int Cout, void* stream) {
   VptConvWgradArgs a = {};
   a.dacc = (const vpt_op16*)dacc; a.x = (const vpt_op16*)x; a.dw = dw; a.partial = scratch;
-  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.OT = 0; a.frames_per_wg = 0;
+  a.frames = frames; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
   CHECK_LAUNCH(vpt_conv_wgrad_launch(&a, (hipStream_t)stream), "vpt_conv3x3_wgrad");
 }
 
@@ -402,7 +398,7 @@ int vpt_layernorm_linear_forward(const float* x, const float* ln_gain, const flo
   VptGemmArgs a{};
   a.ln_x = x; a.ln_gain = ln_gain; a.ln_bias = ln_bias; a.ln_relu_in = relu_in; a.ln_out_f32 = ln_out_f32;
   a.wpk = (const vpt_op16*)wpk; a.bias = bias; a.res = res; a.out_f32 = out_f32; a.out_bf16 = (vpt_op16*)out_bf16;
-  a.M = M; a.N = N; a.K = K; a.lda = K; a.ldr = ldr; a.ldc = ldc; a.ldcb = ldcb; a.relu = relu; a.splitk = 1; a.atomic_out = 0;
+  a.M = M; a.N = N; a.K = K; a.lda = K; a.ldr = ldr; a.ldc = ldc; a.ldcb = ldcb; a.relu = relu; a.splitk = 1;
   CHECK_LAUNCH(vpt_gemm_launch(&a, (hipStream_t)stream), "vpt_layernorm_linear_forward");   // M <= 8: dispatches to vpt_gemv_launch
 }
 
@@ -422,8 +418,8 @@ int vpt_dense_fold_epilogue(const float* part, int splitk, const double* stats, 
 int vpt_linear_splitk_epilogue(const float* part, int splitk, const float* bias, const float* res, float* out_f32, void* out_bf16,
                                int M, int N, int ldr, int ldc, int ldcb, int relu, const void* mask, int ldm, void* stream) {
   VptGemmArgs a{};
-  a.A = nullptr; a.wpk = nullptr; a.bias = bias; a.res = res; a.out_f32 = out_f32; a.out_bf16 = (vpt_op16*)out_bf16;
-  a.M = M; a.N = N; a.K = 0; a.lda = 0; a.ldr = ldr; a.ldc = ldc; a.ldcb = ldcb; a.relu = relu; a.splitk = splitk; a.atomic_out = 0;
+  a.bias = bias; a.res = res; a.out_f32 = out_f32; a.out_bf16 = (vpt_op16*)out_bf16;
+  a.M = M; a.N = N; a.ldr = ldr; a.ldc = ldc; a.ldcb = ldcb; a.relu = relu; a.splitk = splitk;
   a.mask = (const vpt_op16*)mask; a.ldm = ldm;
   CHECK_LAUNCH(vpt_splitk_epilogue_launch(part, splitk, &a, (hipStream_t)stream), "vpt_linear_splitk_epilogue");
 }
@@ -444,9 +440,8 @@ int vpt_layernorm_forward(const float* x, const float* gain, const float* bias, 
 int vpt_masked_attention_forward(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* memvalid,
                                  const float* b_nd, void* out, int B, int t, int heads, int hid, int ld,
                                  int maxlen, int causal, void* stream) {
-  VptAttnArgs a = {};
-  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = memvalid; a.b_nd = b_nd; a.out = (vpt_op16*)out;
-  a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = causal;
+  VptAttnArgs a = attn_args(qkvr, kmem, vmem, b_nd, out, B, t, heads, hid, ld, maxlen);
+  a.memvalid = memvalid; a.causal = causal;
   CHECK_LAUNCH(vpt_attn_launch(&a, (hipStream_t)stream), "vpt_masked_attention_forward");
 }
 
@@ -454,9 +449,8 @@ int vpt_masked_attention_forward_episodes(const float* qkvr, const float* kmem, 
                                           const float* b_nd, void* out, const int32_t* qlo, int B, int t, int heads, int hid, int ld,
                                           int maxlen, void* stream) {
   if (!qlo) return fail(-1, "vpt_masked_attention_forward_episodes: qlo ([B*t] int32, vpt_episode_bounds) is required");
-  VptAttnArgs a = {};
-  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = memvalid; a.b_nd = b_nd; a.out = (vpt_op16*)out; a.qlo = qlo;
-  a.B = B; a.t = t; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = 1;
+  VptAttnArgs a = attn_args(qkvr, kmem, vmem, b_nd, out, B, t, heads, hid, ld, maxlen);
+  a.memvalid = memvalid; a.qlo = qlo;
   CHECK_LAUNCH(vpt_attn_launch(&a, (hipStream_t)stream), "vpt_masked_attention_forward_episodes");
 }
 
@@ -470,18 +464,14 @@ int vpt_episode_bounds(const uint8_t* first, const uint8_t* state_mask, int32_t*
 int vpt_masked_attention_step(const float* qkvr, const float* kmem, const float* vmem, const uint8_t* state_mask, const uint8_t* first,
                               const float* b_nd, void* out, float* kout, float* vout, uint8_t* mask_out,
                               int B, int heads, int hid, int ld, int maxlen, void* stream) {
-  VptAttnArgs a = {};
-  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = nullptr; a.b_nd = b_nd; a.out = (vpt_op16*)out;
-  a.B = B; a.t = 1; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = 1;
+  VptAttnArgs a = attn_args(qkvr, kmem, vmem, b_nd, out, B, /*t=*/1, heads, hid, ld, maxlen);
   CHECK_LAUNCH(vpt_attn_step_launch(&a, state_mask, first, mask_out, kout, vout, nullptr, (hipStream_t)stream), "vpt_masked_attention_step");
 }
 
 int vpt_masked_attention_step_inplace(const float* qkvr, float* kmem, float* vmem, uint8_t* state_mask, const uint8_t* first,
                                       const float* b_nd, void* out, int* done_counter, int B, int heads, int hid, int ld, int maxlen, void* stream) {
   if (!done_counter) return fail(-1, "vpt_masked_attention_step_inplace: done_counter ([B] ints, zero before the first launch) is required");
-  VptAttnArgs a = {};
-  a.qkvr = qkvr; a.kmem = kmem; a.vmem = vmem; a.memvalid = nullptr; a.b_nd = b_nd; a.out = (vpt_op16*)out;
-  a.B = B; a.t = 1; a.heads = heads; a.hid = hid; a.ld = ld; a.maxlen = maxlen; a.causal = 1;
+  VptAttnArgs a = attn_args(qkvr, kmem, vmem, b_nd, out, B, /*t=*/1, heads, hid, ld, maxlen);
   CHECK_LAUNCH(vpt_attn_step_launch(&a, state_mask, first, state_mask, kmem, vmem, done_counter, (hipStream_t)stream), "vpt_masked_attention_step_inplace");
 }
 
@@ -506,9 +496,7 @@ int vpt_kv_memory_update(const float* qkvr, const float* kmem, const float* vmem
 
 int vpt_log_softmax_forward(const float* logits, float* out, int M, int ld, int col0, int n, float temperature,
                             void* stream) {
-  VptLogSoftmaxArgs a = {};
-  a.logits = logits; a.out = out; a.M = M; a.ld = ld; a.col0 = col0; a.n = n; a.temperature = temperature;
-  a.mask = nullptr; a.noise = nullptr; a.action = nullptr; a.action_logp = nullptr; a.rng_state = nullptr; a.rng_stream = 0;
+  VptLogSoftmaxArgs a = log_softmax_args(logits, out, M, ld, col0, n, temperature);
   CHECK_LAUNCH(vpt_logsoftmax_launch(&a, (hipStream_t)stream), "vpt_log_softmax_forward");
 }
 
@@ -516,8 +504,7 @@ int vpt_action_head_forward(const float* logits, const uint8_t* mask, const floa
                             float* out, int64_t* action, float* action_logp, int M, int ld, int col0, int n, float temperature, void* stream) {
   if (action_logp && !action) return fail(-1, "vpt_action_head_forward: action_logp needs action");
   if (noise && rng_state) return fail(-1, "vpt_action_head_forward: give the uniforms (noise) or the generator state (rng_state), not both");
-  VptLogSoftmaxArgs a = {};
-  a.logits = logits; a.out = out; a.M = M; a.ld = ld; a.col0 = col0; a.n = n; a.temperature = temperature;
+  VptLogSoftmaxArgs a = log_softmax_args(logits, out, M, ld, col0, n, temperature);
   a.mask = mask; a.noise = noise; a.action = (long*)action; a.action_logp = action_logp; a.rng_state = rng_state; a.rng_stream = rng_stream;
   CHECK_LAUNCH(vpt_logsoftmax_launch(&a, (hipStream_t)stream), "vpt_action_head_forward");
 }
@@ -526,10 +513,9 @@ int vpt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
                   float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream) {
   if (step < 1) return fail(-1, "vpt_adam_step: step counts from 1");
   VptAdamArgs a = {};
-  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n; a.skip_flag = nullptr;
+  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = (size_t)n;
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
-  a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
-  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  adam_bias_terms(step, lr, beta1, beta2, &a);
   CHECK_LAUNCH(vpt_adam_launch(&a, (hipStream_t)stream), "vpt_adam_step");
 }
 
@@ -538,10 +524,9 @@ static int adam_step_multi_impl(const char* who, const void* table, int ntensors
   if (step < 1) return fail(-1, "vpt_adam_step_multi: step counts from 1");
   if (!table && ntensors > 0) return fail(-1, "vpt_adam_step_multi: null table");
   VptAdamArgs a = {};
-  a.p = nullptr; a.g = nullptr; a.m = nullptr; a.v = nullptr; a.n = 0; a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
+  a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay; a.grad_scale = grad_scale;
-  a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, (double)step)));
-  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  adam_bias_terms(step, lr, beta1, beta2, &a);
   CHECK_LAUNCH(vpt_adam_multi_launch((const VptAdamTensor*)table, ntensors, (long)total_blocks, &a, (hipStream_t)stream), who);
 }
 
@@ -562,10 +547,9 @@ int vpt_adam_step_groups(const void* table, const void* groups, int ntensors, in
   if ((!table || !groups) && ntensors > 0) return fail(-1, "vpt_adam_step_groups: null table / groups");
   if (ntensors < 0 || total_blocks < 0) return fail(-1, "vpt_adam_step_groups: negative tensor / block count");
   VptAdamArgs a = {};
-  a.p = nullptr; a.g = nullptr; a.m = nullptr; a.v = nullptr; a.n = 0; a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = 0.0f; a.grad_scale = grad_scale;
-  a.step_size = 0.0f;      // per tensor: (float)((double)lr / bias_correction1), formed in the kernel
-  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
+  a.skip_flag = (const int*)skip_flag; a.clip_coef = clip_coef;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.grad_scale = grad_scale;      // weight_decay = 0: each tensor's own comes from `groups`
+  a.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));      // step_size stays 0: per tensor, (float)((double)lr / bias_correction1), formed in the kernel
   const double bias_correction1 = 1.0 - pow((double)beta1, (double)step);
   CHECK_LAUNCH(vpt_adam_groups_launch((const VptAdamTensor*)table, (const VptAdamGroup*)groups, ntensors, (long)total_blocks, &a, bias_correction1,
                                       decoupled != 0, (hipStream_t)stream), "vpt_adam_step_groups");

@@ -2,6 +2,10 @@
 
 PyTorch is plumbing here: it owns device memory and the current HIP stream; all arithmetic happens in
 libvpt_hip.so.  Every function requires CUDA(HIP) tensors and raises if the native library is absent.
+
+Argument and return types come from the header (_native.py binds every declaration of it), and so do the VPT_WS_* workspace
+numbers below; a wrapper here only has to pass its arguments in the header's order.  The header is therefore read when this module is
+imported: an unreadable include/vpt_hip.h raises NativeLibraryError at import, not at the first call.
 """
 import ctypes
 import os
@@ -69,9 +73,21 @@ def _call(name, meta, *args, fmt="bf16", label=None):
         _native.call(name, *args, fmt=fmt)
 
 
-WS_CONV3X3_WGRAD, WS_CONV_BACKWARD_PREPARE, WS_LINEAR_SPLITK, WS_LAYERNORM_BACKWARD, WS_COLUMN_SUM = 1, 2, 3, 4, 5      # include/vpt_hip.h VPT_WS_*
-WS_ATTENTION_BACKWARD_DKV, WS_ATTENTION_BACKWARD_DBND, WS_FRAME_AFFINE_BACKWARD, WS_CONV_FIRST_BACKWARD, WS_BC_LOSS = 6, 7, 8, 9, 10
-WS_FULL_ATTENTION_BACKWARD, WS_CONV3D_T5_BACKWARD, WS_RL_LOSS, WS_PPG_AUX_LOSS = 11, 12, 13, 14
+_WS = _native.header().workspace_ops      # include/vpt_hip.h's VPT_WS_* enum, as parsed: the numbers live in the header only
+WS_CONV3X3_WGRAD = _WS["VPT_WS_CONV3X3_WGRAD"]
+WS_CONV_BACKWARD_PREPARE = _WS["VPT_WS_CONV_BACKWARD_PREPARE"]
+WS_LINEAR_SPLITK = _WS["VPT_WS_LINEAR_SPLITK"]
+WS_LAYERNORM_BACKWARD = _WS["VPT_WS_LAYERNORM_BACKWARD"]
+WS_COLUMN_SUM = _WS["VPT_WS_COLUMN_SUM"]
+WS_ATTENTION_BACKWARD_DKV = _WS["VPT_WS_ATTENTION_BACKWARD_DKV"]
+WS_ATTENTION_BACKWARD_DBND = _WS["VPT_WS_ATTENTION_BACKWARD_DBND"]
+WS_FRAME_AFFINE_BACKWARD = _WS["VPT_WS_FRAME_AFFINE_BACKWARD"]
+WS_CONV_FIRST_BACKWARD = _WS["VPT_WS_CONV_FIRST_BACKWARD"]
+WS_BC_LOSS = _WS["VPT_WS_BC_LOSS"]
+WS_FULL_ATTENTION_BACKWARD = _WS["VPT_WS_FULL_ATTENTION_BACKWARD"]
+WS_CONV3D_T5_BACKWARD = _WS["VPT_WS_CONV3D_T5_BACKWARD"]
+WS_RL_LOSS = _WS["VPT_WS_RL_LOSS"]
+WS_PPG_AUX_LOSS = _WS["VPT_WS_PPG_AUX_LOSS"]
 FULL_ATTENTION_MAX_T = 160      # the mask="none" attention kernels' longest window (forward and backward)
 
 
