@@ -351,7 +351,9 @@ int vpt_uniform_noise(const uint64_t* rng_state, uint32_t rng_stream, float* out
 
 /* Fused Adam update of one flat fp32 bucket: th.optim.Adam(lr, weight_decay).step() as configured by
  * behavioural_cloning.py:63-67,122 (L2 weight decay folded into the gradient, bias-corrected moments).
- * `step` counts from 1; grad_scale multiplies the gradient first (1/world_size of the data-parallel mean). */
+ * `step` counts from 1; grad_scale multiplies the gradient first (1/world_size of the data-parallel mean).
+ * The hyper-parameters are taken as fp32 (0.999f, not 0.999: 1 - beta2 is then 0.000999987), and the bias corrections lr / (1 - beta1^step) and
+ * 1 / sqrt(1 - beta2^step) are formed in double from those fp32 values and rounded to fp32 once; the same holds for every entry point below. */
 int vpt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, uint64_t n, int step,
                   float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale, void* stream);
 

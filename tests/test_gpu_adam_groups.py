@@ -1,7 +1,7 @@
 """ops.adam_step_groups_ (vpt_adam_step_groups: one Adam launch with an (lr, weight_decay) per tensor, optionally AdamW's decoupled decay) on the GPU.
 Tensor sizes 1, 3, 1023, 1024, 1025, 4099: the 1024-element block edge and tails of 1..3 elements; two groups interleaved in table order; three
-steps.  The references are the launches the project already holds to torch (ops.adam_step_multi_, tests/test_gpu_kernels.py) and torch.optim.AdamW.
-Needs an MI355X."""
+steps.  The references are ops.adam_step_multi_, which tests/test_gpu_optim_fp64.py holds to an fp64 reference with derived bounds (as it does this
+entry point itself; tests/test_gpu_kernels.py runs the single-tensor ops.adam_step_ only), and torch.optim.AdamW.  Needs an MI355X."""
 import pytest
 import torch
 
