@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["vpt_conv3x3.hip", "vpt_conv3x3_fwd.hip", "vpt_conv3x3_dgrad.hip", "vpt_conv3x3_small.hip", "vpt_conv_first.hip", "vpt_conv3d.hip", "vpt_elementwise.hip", "vpt_gemm.hip", "vpt_gemv.hip", "vpt_action_codec.hip", "vpt_labeler.hip", "vpt_clip.hip", "vpt_augment.hip",
-           "vpt_transformer.hip", "vpt_optim.hip", "vpt_grad_norm.hip", "vpt_backward.hip", "vpt_cnn_backward.hip", "vpt_conv_wgrad.hip", "vpt_conv_first_bwd.hip", "vpt_pack.hip", "vpt_reduce.hip", "vpt_rl.hip", "vpt_ppg.hip", "vpt_rollout.hip", "vpt_lowrank.hip", "vpt_capi.hip"]
+           "vpt_transformer.hip", "vpt_optim.hip", "vpt_grad_norm.hip", "vpt_backward.hip", "vpt_attn_bwd.hip", "vpt_cnn_backward.hip", "vpt_conv_wgrad.hip", "vpt_conv_first_bwd.hip", "vpt_pack.hip", "vpt_reduce.hip", "vpt_rl.hip", "vpt_ppg.hip", "vpt_rollout.hip", "vpt_lowrank.hip", "vpt_capi.hip"]
 LIB = os.path.join(HERE, "libvpt_hip.so")
 LIB_F16 = os.path.join(HERE, "libvpt_hip_f16.so")   # same sources, 16-bit operands = IEEE half (precision="fp16")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-fno-gpu-rdc"]
@@ -28,7 +28,7 @@ REMARKS = ["-Rpass-analysis=kernel-resource-usage"]
 # -fno-slp-vectorize and -O1 do (0 wrong launches in 54 000 against ~85).  vpt_conv3d.hip and vpt_conv_first.hip carry the same instruction in their
 # frame-statistics sums (8 each, compiler-generated); they never failed in the stress, and are built without it as a precaution (+0.006 ms per 1024 frames on the
 # first conv).
-EXTRA_FLAGS = {"vpt_backward.hip": ["-fno-slp-vectorize"], "vpt_rl.hip": ["-fno-slp-vectorize"], "vpt_ppg.hip": ["-fno-slp-vectorize"], "vpt_conv3d.hip": ["-fno-slp-vectorize"], "vpt_conv_first.hip": ["-fno-slp-vectorize"],
+EXTRA_FLAGS = {"vpt_backward.hip": ["-fno-slp-vectorize"], "vpt_attn_bwd.hip": ["-fno-slp-vectorize"], "vpt_rl.hip": ["-fno-slp-vectorize"], "vpt_ppg.hip": ["-fno-slp-vectorize"], "vpt_conv3d.hip": ["-fno-slp-vectorize"], "vpt_conv_first.hip": ["-fno-slp-vectorize"],
                "vpt_grad_norm.hip": ["-fno-slp-vectorize"], "vpt_augment.hip": ["-fno-slp-vectorize"]}      # vpt_augment.hip: the compiler forms such adds in the bilinear sums without it
 VARIANTS = [(LIB, "bf16", []), (LIB_F16, "f16", ["-DVPT_OPERAND_F16"])]
 # Test-only A/B library (never loaded by the product: tests/test_gpu_conv_clamp.py names it through VPT_HIP_LIB): the bf16 library with vpt_conv3x3_fwd.hip's
